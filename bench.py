@@ -25,6 +25,7 @@ HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 
 
 SIDE_SCALE = 1.0          # --side-scale (tests): lengths of the side measurements
+DUMP_ROWS = 1 << 21       # --dump-outputs: rows of x written at most (16 MB, and as much again for their indices)
 
 def main(argv=None, lib=None):
     """`lib` is injected only by tests/test_bench_harness.py (emulator build, tiny sizes)."""
@@ -63,6 +64,9 @@ def main(argv=None, lib=None):
     ap.add_argument("--watchdog-seconds", type=float, default=1500.0,
                     help="dump every thread's Python stack to stderr and exit non-zero if the run takes longer (0 = off): a stalled "
                          "rendezvous or collective then fails with a diagnosis instead of hanging the caller")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed projcg_ call returned as DIR/<name>.npy (float64): x (a fixed seeded "
+                         "sample of its rows when n > %d, the rows in x_rows), nr and iters -- for comparing two builds output for output" % DUMP_ROWS)
     args = ap.parse_args(argv)
     global SIDE_SCALE
     SIDE_SCALE = args.side_scale
@@ -206,6 +210,8 @@ def main(argv=None, lib=None):
         elapsed = float(t[0])
     assert iters == W + K, f"expected {W + K} iterations, got {iters} (nr={nr})"
     assert math.isfinite(nr)
+    if args.dump_outputs:                       # (before anything below runs the solve further)
+        dump_outputs(args.dump_outputs, x, iters, nr, n, r0, rank, dist)
     # the same window five more times (the solve keeps running: K further iterations each) -- `value` is the FIRST window, as the contract
     # says; these show how much one 20-iteration window of ~35 ms scatters
     x_norm = L.nrm2(x)
@@ -351,6 +357,24 @@ def main(argv=None, lib=None):
     if watchdog:
         faulthandler.cancel_dump_traceback_later()
     return out
+
+
+def dump_outputs(d, x, iters, nr, n, r0, rank, dist):
+    """--dump-outputs DIR: what a caller of the timed call receives after its last step -- the iterate x, the residual norm nr and the
+    iteration count -- as float64 .npy files.  x.npy holds the rows named in x_rows.npy: all n of them, or above DUMP_ROWS a fixed seeded
+    sample (the same for every run of the same n).  With N ranks each contributes the sampled rows of its shard; rank 0 writes."""
+    import numpy as np
+    rows = np.arange(n) if n <= DUMP_ROWS else np.sort(np.random.default_rng(2024).choice(n, DUMP_ROWS, replace=False))
+    mine = rows[(rows >= r0) & (rows < r0 + x.n)]
+    vals = x.download()[mine - r0]
+    if dist is not None:
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, vals)             # (shards are contiguous and in rank order: so are the gathered rows)
+        vals = np.concatenate(parts)
+    if rank == 0:
+        os.makedirs(d, exist_ok=True)
+        for name, a in (("x", vals), ("x_rows", rows), ("nr", [nr]), ("iters", [iters])):
+            np.save(os.path.join(d, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def self_launch(args, argv):
