@@ -464,14 +464,18 @@ int lfpsqp_projcg_lowrank(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, co
  *     (A v)_i = (a0 + dg_i) v_i + off_{i-1} v_{i-1} + off_i v_{i+1}      (off: length n, off_i couples rows i and i+1, off_{n-1} is ignored)
  * still ONE pass over U per iteration where lfpsqp_projcg_op pays two.  The projected residual's neighbours do not exist while a pass runs, but
  * gp = rr - U t with t known before the pass and rr = g + alpha A d made of stored vectors: the second product carries A rr (row-local) and the
- * post-op subtracts (U'A U) t; U'A U (m x m) is formed once per solve by two or three weighted Gram passes over U on the matrix cores.  Av: a scratch vector of length(b) (it receives A d of every iteration).  Plain dense basis (materialised or
- * factored, no matrix view), 4 .. 1024 columns, no bounds, one rank, no RESUME / START_PROJECTED (START_GIVEN as for lfpsqp_projcg: r0 and U'r0 do not involve A) -- otherwise
+ * post-op subtracts (U'A U) t; U'A U (m x m) is formed once per solve by two or three weighted Gram passes over U on the matrix cores.  Av: a scratch vector of length(b) (it receives A d of every iteration).  Dense basis (materialised or
+ * factored, no matrix view), 4 .. 1024 columns, one rank, no RESUME / START_PROJECTED (START_GIVEN as for lfpsqp_projcg: r0 and U'r0 do not involve A) -- otherwise
  * LFPSQP_ERR_UNSUPPORTED (use lfpsqp_projcg_op).  Iterates, counts and exits as projcg! with A as a matrix (src/projcg.jl:40-121), to rounding.
- * lfpsqp_tridiag_mul: out = A v (out != v), the operator on its own (mul! of the LinearMap). */
+ * With a STACKED (bound-constrained) basis the operator is the Newton map blockdiag(T, diag) of src/inequality_helper.jl:144-158: dg is a stacked
+ * vector (both halves, as for lfpsqp_diag_op), off holds the x half's couplings (length N; the y half has none), and the pass stays one per
+ * iteration (c != 0 is refused with a stacked basis, as for lfpsqp_projcg).
+ * lfpsqp_tridiag_mul: out = A v (out != v), the operator on its own (mul! of the LinearMap); it takes the same stacked pair (v, out stacked, off of
+ * length N). */
 typedef struct lfpsqp_tridiag_op {
     double a0;
-    const lfpsqp_vec* dg;  /* optional, length n */
-    const lfpsqp_vec* off; /* length n */
+    const lfpsqp_vec* dg;  /* optional, length n (stacked: both halves) */
+    const lfpsqp_vec* off; /* length n (stacked: N, the x half) */
 } lfpsqp_tridiag_op;
 int lfpsqp_projcg_tridiag(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const lfpsqp_tridiag_op* A, lfpsqp_vec* Av, const lfpsqp_basis* U,
                           const lfpsqp_vec* b, const lfpsqp_vec* c, double tol, int64_t maxit, int64_t n_global, int flags,

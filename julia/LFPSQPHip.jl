@@ -718,8 +718,9 @@ function projcg!(x::DeviceVector, λ::Union{Nothing,DeviceVector}, A::LowRankOpe
     end
     return Int(iters[]), nr[]
 end
-# Tridiagonal Hessian: the one-pass iteration where its shape exists (plain dense basis, 4 .. 1024 columns, one rank); otherwise the callback
-# loop below with mul! as the operator -- the same iterates, two passes per iteration.
+# Tridiagonal Hessian: the one-pass iteration where its shape exists (dense basis, plain or stacked, 4 .. 1024 columns, no matrix view, one rank);
+# otherwise the callback loop below with mul! as the operator -- the same iterates, two passes per iteration.  With a stacked basis (bounds)
+# A.dg is the stacked augmented diagonal and A.off the x half's couplings (length N): the Newton map of src/inequality_helper.jl:144-158.
 function projcg!(x::DeviceVector, λ::Union{Nothing,DeviceVector}, A::TridiagonalOperator, U::AnyBasis, b::DeviceVector, c::Union{Nothing,DeviceVector};
                  tol::Float64=1e-6, maxit::Int=length(b) + ncols(U), work::ProjCGWork=ProjCGWork(x, ncols(U)), n_global::Int=length(b),
                  Av::DeviceVector=DeviceVector(x.ctx, length(b)), start_given::Bool=false)
@@ -1451,8 +1452,7 @@ function optimize_core(ctx::HipContext, f, grad!, c!, jac!, hess_lag_vec!, x0::V
     nonlinear_class = c! isa DeviceConstraints && c!.ew !== nothing          # (its Jct may be a view of A, its Hessian term may need A*λ)
     fuse_tangent = factored_basis && param.do_newton && jsp === nothing && m > 0 && ctx.options.fused_tangent_step && !(ineq && nonlinear_class)
     tri_off = diagonal_hessian ? hess_offdiag(hess_lag_vec!) : nothing
-    if tri_off !== nothing
-        ineq && error("a tridiagonal Hessian with bounds: pass hess_lag_vec! as a function (the generic path)")
+    if tri_off !== nothing                                    # (with bounds: the augmented stacked diagonal next to the same couplings)
         ctx.options.tridiagonal_one_pass || (fuse_tangent = false)     # (the callback path starts its solves itself)
         (haskey(VIEW_KEEP, Jct) || ctx.nranks > 1) && (fuse_tangent = false)  # (lfpsqp_projcg_tridiag refuses a matrix view / several ranks: callback path, its own start)
     end                                                       # (the tangent step still hands projcg! r0 and U'r0; never its folded initial projection)

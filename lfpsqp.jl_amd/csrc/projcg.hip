@@ -88,12 +88,14 @@ struct AOpLR {  // A = a0*I + diag(dg) + V diag(sigma) V': (A v)_i = (a0 + dg_i)
 };
 
 // A = a0*I + diag(dg) + tridiagonal couplings: (A v)_i = (a0 + dg_i) v_i + off_{i-1} v_{i-1} + off_i v_{i+1}  (off_i couples rows i and i+1; off_{n-1}
-// is ignored).  lfpsqp_projcg_tridiag / lfpsqp_tridiag_mul.
+// is ignored).  lfpsqp_projcg_tridiag / lfpsqp_tridiag_mul.  Stacked (bound-constrained) vectors [x | gap | y]: the couplings act on the first nc
+// rows (the x half, off of length nc), every other row is diagonal -- the Newton map blockdiag(T + diag, diag) of src/inequality_helper.jl:144-158.
 struct TriD {
     double a0;
     const double* dg;
     const double* off;
     int64_t n;
+    int64_t nc;               // rows with couplings: n, or N of a stacked vector (n = half stride + N)
 };
 struct TriMulF {   // out = A v (a plain vector kernel: the neighbours come out of the cache lines the row itself brings in)
     TriD A;
@@ -103,14 +105,22 @@ struct TriMulF {   // out = A v (a plain vector kernel: the neighbours come out 
     __device__ __forceinline__ bool skip() const { return istat != nullptr && ld_stat(istat + I_STATUS) != ST_RUNNING; }
     __device__ __forceinline__ void apply(int64_t i, bool v0, bool v1, double*) const {
         if (!v0) return;
-        const double2 vv = ld2(v + i), of = ld2(A.off + i);
+        const double2 vv = ld2(v + i);
         const double2 dd = A.dg ? ld2(A.dg + i) : make_double2(0.0, 0.0);
+        if (i + 1 >= A.nc && A.nc < A.n) {                 // stacked: the last x row (no coupling to the gap), the gap and the y half
+            double o0 = (A.a0 + dd.x) * vv.x;
+            if (i < A.nc && i > 0) o0 = fma(A.off[i - 1], v[i - 1], o0);
+            if (!v1) { out[i] = o0; return; }
+            st2(out + i, make_double2(o0, (A.a0 + dd.y) * vv.y));
+            return;
+        }
+        const double2 of = ld2(A.off + i);
         const double vm = (i > 0) ? v[i - 1] : 0.0, om = (i > 0) ? A.off[i - 1] : 0.0;
         double o0 = fma(om, vm, (A.a0 + dd.x) * vv.x);
         if (v1) o0 = fma(of.x, vv.y, o0);
         if (!v1) { out[i] = o0; return; }
         double o1 = fma(of.x, vv.x, (A.a0 + dd.y) * vv.y);
-        if (i + 2 < A.n) o1 = fma(of.y, v[i + 2], o1);
+        if (i + 2 < A.nc) o1 = fma(of.y, v[i + 2], o1);
         st2(out + i, make_double2(o0, o1));
     }
 };
@@ -195,6 +205,99 @@ struct TriPrepF {
 struct StackD {   // stacked (bound-constrained) basis Q = [[diag Dx; diag Dy], [sx.*Z; sy.*Z]]
     int64_t hs;
     const double *Dx, *Dy, *sx, *sy;
+};
+
+// TriPrepF for a stacked basis (PcgFuseTri<true, .>): A = blockdiag(T, diag(ay)) with T = diag(ax) + couplings on the x half (A.n = N rows, the y half
+// at A.dg + hs).  Per row k the pass projects rr = g + alpha A d onto the complement of the diagonal block, u_k = rr_k - D_k (D_k'rr_k) with
+// D_k = (Dx_k, Dy_k), and needs the neighbours' part of (T u)_x:  q_i = off_{i-1} ux_{i-1} + off_i ux_{i+1},  next to  ad_i = (T d)_i  (the x half of
+// A d; the y half ay dy is row-local).  INIT: rr is the stored initial residual, only q is written.  Nine streams of N doubles in, two out (88 N bytes).
+template <bool INIT>
+struct TriPrepSF {
+    TriD A;
+    int64_t hs;
+    const double *Dx, *Dy;
+    const double* g;          // stacked residual (INIT: the stored initial residual)
+    const double* d;          // stacked direction
+    double* ad;               // N: (T d)_x
+    double* q;                // N
+    const double* scal;
+    const int64_t* istat;
+    __device__ __forceinline__ bool skip() const { return ld_stat(istat + I_STATUS) != ST_RUNNING; }
+    __device__ __forceinline__ double at(const double* v, int64_t k) const {      // (clamped index + select, as TriPrepF)
+        const int64_t kc = k < 0 ? 0 : (k >= A.n ? A.n - 1 : k);
+        const double x = v[kc];
+        return (k == kc) ? x : 0.0;
+    }
+    __device__ __forceinline__ double cpl(int64_t k) const {
+        const int64_t kc = k < 0 ? 0 : (k >= A.n ? A.n - 1 : k);
+        const double x = A.off[kc];
+        return (k >= 0 && k + 1 < A.n) ? x : 0.0;
+    }
+    // rows i-1 .. i+2 of a vector (both halves share the row index): one pair load for the thread's own two rows
+    __device__ __forceinline__ void quad(const double* v, int64_t i, double (&o)[4]) const {
+        const double2 c = ld2(v + i);
+        o[0] = v[i - 1]; o[1] = c.x; o[2] = c.y; o[3] = v[i + 2];
+    }
+    __device__ __forceinline__ void apply(int64_t i, bool v0, bool v1, double*) const {
+        if (!v0) return;
+        const double alpha = INIT ? 0.0 : ld_scal(scal + S_ALPHA);
+        double o[5], dxv[6], axv[4], gx[4], gy[4], dy[4], ay[4], Dxv[4], Dyv[4], adv[4], ux[4];
+        if (i >= 2 && i + 4 < A.n) {                                             // interior: aligned pair loads (hs is even)
+            const double2 o0 = ld2(A.off + i - 2), o1 = ld2(A.off + i);
+            o[0] = o0.x; o[1] = o0.y; o[2] = o1.x; o[3] = o1.y; o[4] = A.off[i + 2];
+            quad(g, i, gx); quad(g + hs, i, gy); quad(Dx, i, Dxv); quad(Dy, i, Dyv);
+            if (!INIT) {
+                const double2 d0 = ld2(d + i - 2), d1 = ld2(d + i), d2 = ld2(d + i + 2);
+                dxv[0] = d0.x; dxv[1] = d0.y; dxv[2] = d1.x; dxv[3] = d1.y; dxv[4] = d2.x; dxv[5] = d2.y;
+                quad(d + hs, i, dy);
+                if (A.dg) {
+                    quad(A.dg, i, axv); quad(A.dg + hs, i, ay);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) { axv[k] += A.a0; ay[k] += A.a0; }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) axv[k] = ay[k] = A.a0;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 5; ++k) o[k] = cpl(i - 2 + k);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int64_t r = i - 1 + k;
+                gx[k] = at(g, r); gy[k] = at(g + hs, r); Dxv[k] = at(Dx, r); Dyv[k] = at(Dy, r);
+            }
+            if (!INIT) {
+#pragma unroll
+                for (int k = 0; k < 6; ++k) dxv[k] = at(d, i - 2 + k);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int64_t r = i - 1 + k;
+                    const int64_t rc = r < 0 ? 0 : (r >= A.n ? A.n - 1 : r);
+                    dy[k] = at(d + hs, r);
+                    axv[k] = A.a0 + (A.dg ? A.dg[rc] : 0.0);
+                    ay[k] = A.a0 + (A.dg ? A.dg[hs + rc] : 0.0);
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {                                            // row i - 1 + k; the same expressions as PcgFuseTri<true, .>
+            adv[k] = INIT ? 0.0 : fma(o[k + 1], dxv[k + 2], fma(o[k], dxv[k], axv[k] * dxv[k + 1]));
+            const double rx = INIT ? gx[k] : fma(alpha, adv[k], gx[k]);          // :93
+            const double ry = INIT ? gy[k] : fma(alpha, ay[k] * dy[k], gy[k]);
+            const double ww = Dxv[k] * rx + Dyv[k] * ry;
+            ux[k] = rx - Dxv[k] * ww;
+        }
+        const double q0 = fma(o[2], ux[2], o[1] * ux[0]);
+        const double q1 = fma(o[3], ux[3], o[2] * ux[1]);
+        if (v1) {
+            st2(q + i, make_double2(q0, q1));
+            if (!INIT) st2(ad + i, make_double2(adv[1], adv[2]));
+        } else {
+            q[i] = q0;
+            if (!INIT) ad[i] = adv[1];
+        }
+    }
 };
 
 // ---- K1 -----------------------------------------------------------------------
@@ -564,21 +667,34 @@ struct PcgFuseLR {
 //                                                step alpha A d left in the range of U: no cancellation beyond a digit or two);
 //   gp'A d, d'A d: row-local with A d stored.
 // The row record has five doubles instead of three, the matrix stream is untouched, the residual is updated in place as in the diagonal form.
-template <bool INIT>
+//
+// ST: stacked (bound-constrained) basis Q = [[diag Dx; diag Dy], [sx.*Z; sy.*Z]] and A = blockdiag(T, diag(ay)), T = diag(ax) + couplings on the x
+// half (src/inequality_helper.jl:144-158).  (sx, sy) = Dy (Dy, -Dx) is orthogonal to (Dx, Dy) but not of unit length; nothing below assumes it.
+// Per row, ww = Dx rx + Dy ry (the diagonal block of Q'rr) and  u = rr - (Dx, Dy) ww  are row-local, and gp = u - (sx, sy) (Z t) as in PcgFuseE.
+// With Q_Z = [sx.*Z; sy.*Z] the split above holds with u in the place of rr:
+//   Q_Z'(A gp) = Z'(sx.*(ax.*ux + q) + sy.*ay.*uy) - M t,   q_i = off_{i-1} ux_{i-1} + off_i ux_{i+1}  (TriPrepSF),
+//                M = Q_Z'A Q_Z = Z' At Z,  At tridiagonal: At_ii = sx_i^2 ax_i + sy_i^2 ay_i,  At_{i,i+1} = sx_i off_i sx_{i+1}  (tri_stack_weights_kernel);
+//   gp'A gp    = u'A u - 2 t'(Q_Z'A u) + t'M t,   u'A u = sum ux (ax ux + q) + ay uy^2   (PcgPostF's triM path unchanged);
+//   rr'gp, gp'gp, gp'A d, d'A d: row-local, with (A d)_x = (T d)_x stored by TriPrepSF and (A d)_y = ay dy formed here.
+// The record is PcgFuseE<true, .>'s plus A d and q: twelve doubles, 8 n m + 112 n bytes per pass next to TriPrepSF's 88 n.
+template <bool ST, bool INIT>
 struct PcgFuseTri {
     const double* rp;
     const double* g;
     double* gout;
     double* d;
-    const double* ad;     // A d of the current direction       (TriPrepF; unused by INIT)
-    const double* q;      // off-diagonal part of A rr          (TriPrepF)
+    const double* ad;     // A d of the current direction       (TriPrepF; unused by INIT)   stacked: the x half (T d)_x
+    const double* q;      // off-diagonal part of A rr          (TriPrepF)                   stacked: ... of (T u)_x (TriPrepSF)
     AOpD A;               // the diagonal of the operator
     const double* scal;
     const int64_t* istat;
+    StackD k;             // stacked only
     static constexpr bool kSplitRed = true;
     static constexpr bool kNoRowScale = true;
     struct Uni { double alpha; };
-    struct Row { double gx, dx, ax, ad, q; };
+    struct RowP { double gx, dx, ax, ad, q; };
+    struct RowS { double gx, dx, ax, gy, dy, ay, Dx, Dy, sx, sy, ad, q; };
+    using Row = std::conditional_t<ST, RowS, RowP>;
     static __device__ __forceinline__ double at(const double* base, uint32_t o) {
         return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(base) + o);
     }
@@ -594,32 +710,65 @@ struct PcgFuseTri {
         w.ax = A.a0 + (A.dg ? at(A.dg, o) : 0.0);
         w.ad = INIT ? 0.0 : at(ad, o);
         w.q = at(q, o);
+        if constexpr (ST) {
+            w.gy = INIT ? at(rp + k.hs, o) : at(g + k.hs, o);
+            w.dy = INIT ? 0.0 : at(d + k.hs, o);
+            w.ay = A.a0 + (A.dg ? at(A.dg + k.hs, o) : 0.0);
+            w.Dx = at(k.Dx, o); w.Dy = at(k.Dy, o); w.sx = at(k.sx, o); w.sy = at(k.sy, o);
+        }
         return w;
     }
-    static constexpr int kStageStreams = INIT ? 0 : 1;
-    __device__ __forceinline__ double* stage_out(int) const { return gout; }
+    // staged form: as PcgFuseE (stacked: the x and the y half of the residual)
+    static constexpr int kStageStreams = INIT ? 0 : (ST ? 2 : 1);
+    __device__ __forceinline__ double* stage_out(int sv) const { return sv == 0 ? gout : gout + k.hs; }
     __device__ __forceinline__ void apply(int64_t row, uint32_t o, const double (&accv)[1], bool valid, bool owner, bool lead, const Uni& u,
                                           const Row& w, double (&v)[2], double (&red)[2]) const {
         apply_staged(row, o, accv, valid, owner, lead, u, w, v, red, nullptr, 0);
     }
-    // reductions, logical order: rp'gp, gp'gp, rr'A rr, gp'A d | d'A d  (kSplitRed, as PcgFuseE)
+    // reductions, logical order: rp'gp, gp'gp, rr'A rr (stacked: u'A u), gp'A d | d'A d  (kSplitRed, as PcgFuseE)
     __device__ __forceinline__ void apply_staged(int64_t, uint32_t o, const double (&accv)[1], bool valid, bool owner, bool lead, const Uni& u,
-                                                 const Row& w, double (&v)[2], double (&red)[2], double* slot, int) const {
+                                                 const Row& w, double (&v)[2], double (&red)[2], double* slot, int sstride) const {
         const int h = (int)((threadIdx.x >> 2) & 3u);
-        const double rr = INIT ? w.gx : fma(u.alpha, w.ad, w.gx);                // :93 (TriPrepF formed the neighbours' rr by the same fma)
-        const double gp = rr - accv[0];                                          // :97
-        const double ar = fma(w.ax, rr, w.q);                                    // (A rr)_i
-        if (valid && owner) {
-            if (slot) *slot = gp;
-            else put(gout, o, gp);
-            if (INIT) put(d, o, -gp);                                            // :62
+        if constexpr (!ST) {
+            const double rr = INIT ? w.gx : fma(u.alpha, w.ad, w.gx);                // :93 (TriPrepF formed the neighbours' rr by the same fma)
+            const double gp = rr - accv[0];                                          // :97
+            const double ar = fma(w.ax, rr, w.q);                                    // (A rr)_i
+            if (valid && owner) {
+                if (slot) *slot = gp;
+                else put(gout, o, gp);
+                if (INIT) put(d, o, -gp);                                            // :62
+            }
+            if (valid && lead) {
+                red[0] += (h == 2) ? rr * ar : gp * ((h == 0) ? rr : ((h == 1) ? gp : w.ad));
+                if (h == 0) red[1] += w.dx * w.ad;                                   // d'Ad
+            }
+            v[0] = valid ? gp : 0.0;
+            v[1] = valid ? ar : 0.0;
+        } else {
+            const double acc = accv[0];
+            const double ady = w.ay * w.dy;
+            const double rx = INIT ? w.gx : fma(u.alpha, w.ad, w.gx);                // :93 (TriPrepSF: the same expressions for the neighbours)
+            const double ry = INIT ? w.gy : fma(u.alpha, ady, w.gy);
+            const double ww = w.Dx * rx + w.Dy * ry;                                 // diagonal block of Q'rp
+            const double ux = rx - w.Dx * ww, uy = ry - w.Dy * ww;
+            const double gx = rx - fma(w.sx, acc, w.Dx * ww);                        // :97, as PcgFuseE<true, .>
+            const double gy = ry - fma(w.sy, acc, w.Dy * ww);
+            const double aux = fma(w.ax, ux, w.q), auy = w.ay * uy;                  // (A u)_i
+            if (valid && owner) {
+                if (slot) { slot[0] = gx; slot[sstride] = gy; }
+                else { put(gout, o, gx); put(gout + k.hs, o, gy); }
+                if (INIT) { put(d, o, -gx); put(d + k.hs, o, -gy); }                 // :62
+            }
+            if (valid && lead) {
+                const double px = (h == 2) ? ux : gx, py = (h == 2) ? uy : gy;
+                const double fx = (h == 0) ? rx : ((h == 1) ? gx : ((h == 2) ? aux : w.ad));
+                const double fy = (h == 0) ? ry : ((h == 1) ? gy : ((h == 2) ? auy : ady));
+                red[0] += fx * px + fy * py;
+                if (h == 0) red[1] += w.dx * w.ad + w.dy * ady;                      // d'Ad
+            }
+            v[0] = valid ? (w.sx * gx + w.sy * gy) : 0.0;                            // the Z-block of Q'g
+            v[1] = valid ? (w.sx * aux + w.sy * auy) : 0.0;                          // ... of Q'(A u)
         }
-        if (valid && lead) {
-            red[0] += (h == 2) ? rr * ar : gp * ((h == 0) ? rr : ((h == 1) ? gp : w.ad));
-            if (h == 0) red[1] += w.dx * w.ad;                                   // d'Ad
-        }
-        v[0] = valid ? gp : 0.0;
-        v[1] = valid ? ar : 0.0;
     }
 };
 
@@ -1074,6 +1223,20 @@ __global__ __launch_bounds__(256) void tri_weights_kernel(TriD A, double* __rest
     }
     if (neg) *anyneg = 1.0;
 }
+// stacked basis: the reduced operator Q_Z'A Q_Z = Z' At Z of the tridiagonal At = S_x T S_x + S_y diag(ay) S_y (PcgFuseTri<true, .>) -- the same Gram
+// passes as above, over At instead of A
+__global__ __launch_bounds__(256) void tri_stack_weights_kernel(TriD A, int64_t hs, const double* __restrict__ sx, const double* __restrict__ sy,
+                                                                double* __restrict__ adg, double* __restrict__ aoff, int64_t npad) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < npad; i += (int64_t)gridDim.x * 256) {
+        double dv = 0.0, ov = 0.0;
+        if (i < A.n) {
+            const double ax = A.a0 + (A.dg ? A.dg[i] : 0.0), ay = A.a0 + (A.dg ? A.dg[hs + i] : 0.0);
+            dv = fma(sx[i] * sx[i], ax, sy[i] * sy[i] * ay);
+            if (i + 1 < A.n) ov = sx[i] * A.off[i] * sx[i + 1];
+        }
+        adg[i] = dv; aoff[i] = ov;
+    }
+}
 static int ensure_tri(lfpsqp_ctx* ctx, size_t doubles) {
     if (doubles <= ctx->tri_cap) return 0;
     LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1084,15 +1247,26 @@ static int ensure_tri(lfpsqp_ctx* ctx, size_t doubles) {
     ctx->tri_cap = doubles;
     return 0;
 }
-// Mh (m x m, column-major, host) = U'A U for U = Z[:, :mc] (W == nullptr, m == mc) or U = Z[:, :mc] W (W: mc x m, host)
-static int tri_reduced_operator(lfpsqp_ctx* ctx, const lfpsqp_mat* Z, int mc, const TriD& A, const double* W, int m, std::vector<double>& Mh) {
-    const int64_t n = A.n, npad = round_up((n > 0 ? n : 1) + 1, kPadRows);
-    LF_TRY(ensure_tri(ctx, 4 * (size_t)npad + 8));
+// Mh (m x m, column-major, host) = U'A U for U = Z[:, :mc] (W == nullptr, m == mc) or U = Z[:, :mc] W (W: mc x m, host); sk: a stacked basis,
+// U = [sx; sy] .* (that), and A over the x half (A.n = N rows, dg stacked)
+static int tri_reduced_operator(lfpsqp_ctx* ctx, const lfpsqp_mat* Z, int mc, const TriD& A0, const double* W, int m, std::vector<double>& Mh,
+                                const StackD* sk = nullptr) {
+    const int64_t n = A0.n, npad = round_up((n > 0 ? n : 1) + 1, kPadRows);
+    LF_TRY(ensure_tri(ctx, (sk ? 6 : 4) * (size_t)npad + 8));
     double* wabs = ctx->d_tri;
     double* sgn = wabs + npad;
     double* cpos = sgn + npad;
     double* cneg = cpos + npad;
     double* anyneg = cneg + npad;
+    TriD A = A0;
+    if (sk) {
+        double* adg = anyneg + 8;
+        double* aoff = adg + npad;
+        hipLaunchKernelGGL(tri_stack_weights_kernel, dim3((int)std::min<int64_t>((npad + 255) / 256, 4096)), dim3(256), 0, ctx->stream, A0, sk->hs, sk->sx,
+                           sk->sy, adg, aoff, npad);
+        LF_LAUNCH_CHECK(ctx);
+        A = TriD{0.0, adg, aoff, n, n};
+    }
     LF_HIP(ctx, hipMemsetAsync(anyneg, 0, sizeof(double), ctx->stream));
     hipLaunchKernelGGL(tri_weights_kernel, dim3((int)std::min<int64_t>((npad + 255) / 256, 4096)), dim3(256), 0, ctx->stream, A, wabs, sgn, cpos, cneg, npad, anyneg);
     LF_LAUNCH_CHECK(ctx);
@@ -1238,14 +1412,17 @@ static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const
     }
     // tridiagonal operator (lfpsqp_projcg_tridiag): fused iteration only; M = U'A U first (its Gram passes use the scratch areas reserved below)
     std::vector<double> triMh;
-    TriD Atri{0.0, nullptr, nullptr, 0};
+    TriD Atri{0.0, nullptr, nullptr, 0, 0};
+    TriD AtriMul = Atri;                               // the operator over whole (stacked) vectors: lfpsqp_tridiag_mul's form
     if (TRop) {
-        LF_ARG(ctx, TRop->off && TRop->off->n == nv && (!TRop->dg || TRop->dg->n == nv));
-        if (!fused || stacked || !plain_mat(Z) || ctx->comm_active())
-            return set_err(ctx, LFPSQP_ERR_UNSUPPORTED, "lfpsqp_projcg_tridiag: needs the one-pass iteration over a plain dense basis (4 .. 1024 columns, no matrix "
-                                                        "view, no bounds) on a single rank (the couplings would cross the shard boundaries); use lfpsqp_projcg_op");
-        Atri = TriD{TRop->a0, TRop->dg ? TRop->dg->p : nullptr, TRop->off->p, nv};
-        LF_TRY(tri_reduced_operator(ctx, Z, mc, Atri, DF ? U->W : nullptr, m, triMh));
+        // (stacked: dg over both halves, off the x half's couplings -- length N; the y half is diagonal)
+        LF_ARG(ctx, TRop->off && TRop->off->n == N && (!TRop->dg || TRop->dg->n == nv));
+        if (!fused || !plain_mat(Z) || ctx->comm_active())
+            return set_err(ctx, LFPSQP_ERR_UNSUPPORTED, "lfpsqp_projcg_tridiag: needs the one-pass iteration over a dense basis (4 .. 1024 columns, no matrix "
+                                                        "view) on a single rank (the couplings would cross the shard boundaries); use lfpsqp_projcg_op");
+        Atri = TriD{TRop->a0, TRop->dg ? TRop->dg->p : nullptr, TRop->off->p, N, N};
+        AtriMul = TriD{Atri.a0, Atri.dg, Atri.off, nv, N};
+        LF_TRY(tri_reduced_operator(ctx, Z, mc, Atri, DF ? U->W : nullptr, m, triMh, stacked ? &sk : nullptr));
     }
     double* dTriM = nullptr;
     double *lrUtV = nullptr, *lrSig = nullptr, *lrVdraw = nullptr, *lrVdc = nullptr, *lrVtv = nullptr;
@@ -1309,7 +1486,7 @@ static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const
             return residual_with(AOpLR{Ad.a0, Ad.dg, LRop->V->p, LRop->V->ld, kLR, lrSig, lrVtv}, sgn, store, t_out);
         }
         if (TRop) {                                                           // Av = A x by the stencil kernel, then as a stored product
-            LF_TRY((run_vec<TriMulF, 0, NoPost>(ctx, nv, TriMulF{Atri, x->p, Av->p, nullptr}, 0u, nullptr, NoPost())));
+            LF_TRY((run_vec<TriMulF, 0, NoPost>(ctx, nv, TriMulF{AtriMul, x->p, Av->p, nullptr}, 0u, nullptr, NoPost())));
             return residual_with(Aop, sgn, store, t_out);
         }
         if (!opf) return residual_with(Ad, sgn, store, t_out);
@@ -1361,12 +1538,19 @@ static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const
         const double* tin = DF ? uDF : Utr;               // coefficients of the first product over the streamed matrix's mc columns
         double* Tout = DF ? Traw : T12;
         // tridiagonal: the neighbours' contributions first (a vector kernel), into Av while rp still holds the initial residual, into rp afterwards
-        if (TRop && init) {
+        // (stacked: both into the first N entries)
+        if (TRop && stacked && init) {
+            LF_TRY((run_vec<TriPrepSF<true>, 0, NoPost>(ctx, N, TriPrepSF<true>{Atri, hs, sk.Dx, sk.Dy, rp, nullptr, nullptr, Av->p, scal, istat}, 0u, nullptr, NoPost())));
+            LF_TRY((run_onepass<PcgFuseTri<true, true>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseTri<true, true>{rp, gin, gout, d, nullptr, Av->p, Ad, scal, istat, sk}, Tout, slot)));
+        } else if (TRop && stacked) {
+            LF_TRY((run_vec<TriPrepSF<false>, 0, NoPost>(ctx, N, TriPrepSF<false>{Atri, hs, sk.Dx, sk.Dy, gin, d, Av->p, rp, scal, istat}, 0u, nullptr, NoPost())));
+            LF_TRY((run_onepass<PcgFuseTri<true, false>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseTri<true, false>{rp, gin, gout, d, Av->p, rp, Ad, scal, istat, sk}, Tout, slot)));
+        } else if (TRop && init) {
             LF_TRY((run_vec<TriPrepF<true>, 0, NoPost>(ctx, nv, TriPrepF<true>{Atri, rp, nullptr, nullptr, Av->p, scal, istat}, 0u, nullptr, NoPost())));
-            LF_TRY((run_onepass<PcgFuseTri<true>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseTri<true>{rp, gin, gout, d, nullptr, Av->p, Ad, scal, istat}, Tout, slot)));
+            LF_TRY((run_onepass<PcgFuseTri<false, true>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseTri<false, true>{rp, gin, gout, d, nullptr, Av->p, Ad, scal, istat, sk}, Tout, slot)));
         } else if (TRop) {
             LF_TRY((run_vec<TriPrepF<false>, 0, NoPost>(ctx, nv, TriPrepF<false>{Atri, gin, d, Av->p, rp, scal, istat}, 0u, nullptr, NoPost())));
-            LF_TRY((run_onepass<PcgFuseTri<false>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseTri<false>{rp, gin, gout, d, Av->p, rp, Ad, scal, istat}, Tout, slot)));
+            LF_TRY((run_onepass<PcgFuseTri<false, false>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseTri<false, false>{rp, gin, gout, d, Av->p, rp, Ad, scal, istat, sk}, Tout, slot)));
         }
         else if (kLR > 0 && init) LF_TRY((run_onepass<PcgFuseLR<true>, 2, 5 + kLRMax>(ctx, Z, mc, mc, N, tin, PcgFuseLR<true>{rp, gin, gout, d, Ad, scal, istat, LRop->V->p, LRop->V->ld, kLR, lrVdc}, Tout, slot)));
         else if (kLR > 0) LF_TRY((run_onepass<PcgFuseLR<false>, 2, 5 + kLRMax>(ctx, Z, mc, mc, N, tin, PcgFuseLR<false>{rp, gin, gout, d, Ad, scal, istat, LRop->V->p, LRop->V->ld, kLR, lrVdc}, Tout, slot)));
@@ -1578,10 +1762,13 @@ extern "C" int lfpsqp_projcg_tridiag(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec*
 }
 
 extern "C" int lfpsqp_tridiag_mul(lfpsqp_ctx* ctx, const lfpsqp_tridiag_op* A, const lfpsqp_vec* v, lfpsqp_vec* out) {
-    LF_ARG(ctx, ctx && A && A->off && v && out && v != out && v->p != out->p && out->n == v->n && A->off->n == v->n && (!A->dg || A->dg->n == v->n));
+    // off of length n, or of length N for a stacked pair (v->n = half stride + N: the couplings act on the x half, the rest is diagonal)
+    LF_ARG(ctx, ctx && A && A->off && v && out && v != out && v->p != out->p && out->n == v->n && (!A->dg || A->dg->n == v->n));
+    LF_ARG(ctx, A->off->n == v->n || (A->off->n > 0 && v->n == lfpsqp_half_stride(A->off->n) + A->off->n));
     if (ctx->comm_active())        // (a rank sees its own rows only: the couplings across the shard boundaries would silently drop out)
         return set_err(ctx, LFPSQP_ERR_UNSUPPORTED, "lfpsqp_tridiag_mul: one rank only (no halo exchange between row shards)");
-    return run_vec<TriMulF, 0, NoPost>(ctx, v->n, TriMulF{TriD{A->a0, A->dg ? A->dg->p : nullptr, A->off->p, v->n}, v->p, out->p, nullptr}, 0u, nullptr, NoPost());
+    return run_vec<TriMulF, 0, NoPost>(ctx, v->n, TriMulF{TriD{A->a0, A->dg ? A->dg->p : nullptr, A->off->p, v->n, A->off->n}, v->p, out->p, nullptr}, 0u, nullptr,
+                                       NoPost());
 }
 
 extern "C" int lfpsqp_projcg_op(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, lfpsqp_opfun A, void* user, lfpsqp_vec* Av,

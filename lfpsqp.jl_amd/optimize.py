@@ -213,11 +213,11 @@ def optimize_core(f, grad_, c_, jac_, hess_lag_vec_, x0, xl, xu, m: int, param: 
     ineqproject = InequalityDecompProject(idecomp) if ineq else None
 
     # a TRIDIAGONAL Lagrangian Hessian: ``diag_`` fills the diagonal, ``offdiag`` (device n-vector, entry i couples variables i and i+1) holds the
-    # couplings -- projcg_ keeps one pass per iteration with it (lfpsqp_projcg_tridiag; no bounds, one rank: the operator's own limits)
+    # couplings -- projcg_ keeps one pass per iteration with it (lfpsqp_projcg_tridiag; one rank: the operator's own limit).  With bounds the
+    # Newton map is blockdiag(H + 2 lamy.*q, 2 lamy.*s) (src/inequality_helper.jl:144-158): the augmented diagonal (stacked, lfpsqp_augmented_diag
+    # or the tangent step, as for a diagonal Hessian) next to the same couplings on the x half
     tri_off = getattr(hess_lag_vec_, "offdiag", None) if diagonal_hessian else None
     if tri_off is not None:
-        if ineq:
-            raise NotImplementedError("a tridiagonal Hessian with bounds: pass hess_lag_vec_ as a callable (the generic path)")
         # (the tangent step's pass still hands projcg_ r0 and U'r0 -- neither involves A --, but never its folded initial projection, whose
         # sums are formed with the diagonal alone: init_fold stays off below)
         if not bool(getattr(ctx.options, "tridiagonal_one_pass", True)):

@@ -106,5 +106,6 @@ class DeviceOptions:
     fused_tangent_step: bool = True
     # a problem class with a TRIDIAGONAL Lagrangian Hessian (an ``offdiag`` vector next to ``diag_``) gets its truncated-Newton solves on the one-pass
     # iteration (lfpsqp_projcg_tridiag: U'AU by two or three Gram passes per solve, then 1.85 instead of 3.3 ms per iteration at (1e7, 128) -- ahead
-    # from six to nine iterations per solve on).  False: the same operator through the callback path (lfpsqp_projcg_op), identical iterates
+    # from six to nine iterations per solve on; with bounds the stacked form of the same pass).  False: the same operator through the callback path
+    # (lfpsqp_projcg_op), identical iterates
     tridiagonal_one_pass: bool = True

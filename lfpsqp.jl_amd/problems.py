@@ -167,33 +167,50 @@ class SeparableLinearBallBox(QuadLinearBallBox):
 class ChainSeparableLinear(SeparableLinearBallBox):
     """A separable objective plus a CHAIN term: f(x) = sum_i phi(x_i - c_i; a_i) + kappa/2 sum_{i<n-1} (x_{i+1} - x_i)^2 (smoothing / first
     differences -- the kind of objective whose Hessian the reference reaches only through hess_lag_vec!, src/autodiff_generators.jl:72-107)
-    under dense linear equalities.  The Lagrangian Hessian is TRIDIAGONAL: diagonal phi''(x_i) + kappa deg_i (deg = 1 at the two ends, 2
-    inside), couplings -kappa.  ``optimize`` hands it to projcg_ as a :class:`TridiagonalOperator` (``offdiag`` below): the truncated-Newton
-    solves keep one pass over the basis per iteration (lfpsqp_projcg_tridiag).  One rank, no ball, no bounds (the one-pass form's limits)."""
+    under dense linear equalities, with the optional ball (slack variable) and box bounds of :class:`QuadLinearBallBox`.  The Lagrangian Hessian
+    is TRIDIAGONAL: diagonal phi''(x_i) + kappa deg_i (+ 2 lam_ball; deg = 1 at the two ends, 2 inside), couplings -kappa; the slack row, when
+    the ball is there, has neither.  ``optimize`` hands it to projcg_ as a :class:`TridiagonalOperator` (``offdiag`` below; with bounds the
+    augmented stacked diagonal next to the same couplings): the truncated-Newton solves keep one pass over the basis per iteration
+    (lfpsqp_projcg_tridiag).  One rank (the couplings would cross the shard boundaries)."""
 
     def __init__(self, ctx: Context, n: int, m: int, Jct: DeviceMatrix, b, kind: int, a, c=0.0, kappa: float = 1.0, **kw):
-        assert kw.get("R2") is None and kw.get("xl") is None and kw.get("xu") is None, "chain objective: equalities only"
         assert kw.get("n_global", n) in (None, n), "chain objective: one rank (the couplings would cross the shard boundaries)"
         super().__init__(ctx, n, m, Jct, b, kind, a, c, **kw)
         from .projcg import TridiagonalOperator
         self.kappa = float(kappa)
-        deg = np.full(n, 2.0 * self.kappa)
-        deg[0] = deg[-1] = self.kappa if n > 1 else 0.0
-        self._deg = ctx.vector(n, deg)
-        self.offdiag = ctx.vector(n, np.full(n, -self.kappa))             # (entry n-1 is ignored)
+        N = self.N                                                        # n, or n + 1 with the ball's slack variable (no chain term on it)
+        deg = np.zeros(N)
+        deg[:n] = 2.0 * self.kappa
+        deg[0] = deg[n - 1] = self.kappa if n > 1 else 0.0
+        off = np.full(N, -self.kappa)
+        off[n - 1:] = 0.0                                                 # (entry n-1 would couple the last variable to the slack row; N-1 is ignored)
+        self._deg = ctx.vector(N, deg)
+        self.offdiag = ctx.vector(N, off)
         self._lap = TridiagonalOperator(0.0, self._deg, self.offdiag)     # kappa * L, L = the path graph's Laplacian
-        self._tmp = ctx.vector(n)
+        self._tmp = ctx.vector(N)
+        self._lap2 = self._tmp2 = None                                    # the same over stacked iterates [x | gap | y] (bounds): zero on the y half
+
+    def _chain(self, x: DeviceVector):
+        """tmp = kappa L x (x plain, or stacked: the x half)."""
+        if x.n == self.N:
+            return self._lap.mul_(self._tmp, x)
+        if self._lap2 is None:
+            from .inequality import StackedVector
+            from .projcg import TridiagonalOperator
+            deg2 = StackedVector(self.ctx, self.N)
+            deg2.copy_range_from(self._deg, self.N)
+            self._lap2 = TridiagonalOperator(0.0, deg2, self.offdiag)
+            self._tmp2 = StackedVector(self.ctx, self.N)
+        return self._lap2.mul_(self._tmp2, x)
 
     def f(self, x: DeviceVector) -> float:
         from .device import dot
-        self._lap.mul_(self._tmp, x)
-        return super().f(x) + 0.5 * dot(x, self._tmp)
+        return super().f(x) + 0.5 * dot(x, self._chain(x))
 
     def grad_(self, g: DeviceVector, x: DeviceVector):
         from .device import axpby
         super().grad_(g, x)
-        self._lap.mul_(self._tmp, x)
-        axpby(1.0, self._tmp, 1.0, g)
+        axpby(1.0, self._chain(x), 1.0, g)
 
     def diag_objective_(self, hx: DeviceVector, x: DeviceVector):
         from .device import axpby

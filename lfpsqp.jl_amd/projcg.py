@@ -98,7 +98,10 @@ class TridiagonalOperator:
     """(A v)_i = (a0 + dg_i) v_i + off_{i-1} v_{i-1} + off_i v_{i+1} (lfpsqp_tridiag_op): a diagonal Hessian plus nearest-neighbour
     couplings.  ``off``: DeviceVector of length n (entry i couples rows i and i+1; the last entry is ignored).  On a :class:`DeviceBasis`
     projcg_ runs it on the fused ONE-pass iteration (lfpsqp_projcg_tridiag); ``mul_`` is the operator on its own (lfpsqp_tridiag_mul), which
-    the generic loop / lfpsqp_projcg_op use -- two passes over the basis per iteration."""
+    the generic loop / lfpsqp_projcg_op use -- two passes over the basis per iteration.
+    With bounds (a stacked basis, :class:`InequalityDecompProject`): ``dg`` is a :class:`StackedVector` (the augmented diagonal, both halves)
+    and ``off`` has N entries, the couplings of the x half -- the Newton map blockdiag(T, diag) of src/inequality_helper.jl:144-158, on the same
+    one-pass iteration."""
 
     def __init__(self, a0: float, dg: DeviceVector | None, off: DeviceVector):
         self.a0, self.dg, self.off = float(a0), dg, off
@@ -263,7 +266,7 @@ def projcg_(x: DeviceVector, lam: DeviceVector | None, A, U, b: DeviceVector, c:
         if rc != -5:                 # LFPSQP_ERR_UNSUPPORTED (a shape without the one-pass iteration): the callback path below
             ctx.check(rc)
             return iters.value, nr.value
-    if isinstance(A, TridiagonalOperator) and isinstance(U, DeviceBasis) and not stacked and not (resume or start_projected) and getattr(A, "fused", True):
+    if isinstance(A, TridiagonalOperator) and (isinstance(U, DeviceBasis) or stacked) and not (resume or start_projected) and getattr(A, "fused", True):
         if getattr(work, "Av", None) is None:
             work.Av = DeviceVector(ctx, n)
         iters = _capi.c_i64()
