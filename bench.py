@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: projected-CG iterations/s at n=1e7, m=128, fp64
-(BASELINE.json metric), with the achieved HBM GB/s of the J / J' matvec kernels.
+(BASELINE.json metric), with the achieved HBM GB/s of the J / J' matvec kernels (--full).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the line: `value`, `ms_per_step`,
+the roofline and per-kernel figures of the timed steps themselves (HIP events), `check`.  Everything that takes runs of its own
+-- further timed windows, the single-call rate, the plain matvecs, the single-GPU `extras` and the CPU baseline -- and the
+first-allocation estimate come only with --full.
 
 A "step" is one projected-CG iteration (src/projcg.jl:71-112 of the reference) on the
 synthetic sustained-iteration workload of SURVEY §8(d): U = n x m basis, A = diag(1 + 9 (u + 1) / 2) = diag(5.5 + 4.5 u)
@@ -39,8 +44,12 @@ def main(argv=None, lib=None):
     ap.add_argument("--prewarm-seconds", type=float, default=2.0,
                     help="untimed device warm-up before the W warmup steps: the same iteration loop for this long, so that a GPU that "
                          "was idle (low-power state) is timed in its steady state; 0 = off")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the tangent-setup / Newton-retraction timings (not part of `value`)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what takes runs of its own (none of it touches `value` or the dumped outputs): five "
+                         "further timed windows, the same K iterations as one fresh call, the plain matvecs, the first-allocation estimate, and "
+                         "on one GPU the `extras` and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="(with --full) skip the tangent-setup / Newton-retraction timings (not part of `value`)")
     ap.add_argument("--cpu-sample-n", type=float, default=2e6)
     ap.add_argument("--side-scale", type=float, default=1.0,
                     help="(tests) scale of the SIDE measurements' lengths -- iterations of the Newton / pcg! timings in `extras`, CPU seconds and the host "
@@ -212,27 +221,28 @@ def main(argv=None, lib=None):
     assert math.isfinite(nr)
     if args.dump_outputs:                       # (before anything below runs the solve further)
         dump_outputs(args.dump_outputs, x, iters, nr, n, r0, rank, dist)
-    # the same window five more times (the solve keeps running: K further iterations each) -- `value` is the FIRST window, as the contract
-    # says; these show how much one 20-iteration window of ~35 ms scatters
     x_norm = L.nrm2(x)
-    more_windows = []
-    if world == 1 and resumed:
-        L.projcg_(x, None, A, U, b, None, tol=1e-300, maxit=W, work=work, n_global=n, want_lambda=False)      # (the norm above ended the first solve)
-        for _ in range(5):
-            ctx.sync(); t0w = time.perf_counter()
-            L.projcg_(x, None, A, U, b, None, tol=1e-300, maxit=K, work=work, n_global=n, want_lambda=False, resume=True)
-            ctx.sync(); more_windows.append(K / (time.perf_counter() - t0w))
-    # the same K iterations as ONE fresh call (set-up inside the clock): what a caller of projcg! with maxit = K sees
-    barrier()
-    t0 = time.perf_counter()
-    L.projcg_(x, None, A, U, b, None, tol=1e-300, maxit=K, work=work, n_global=n, want_lambda=False)
-    ctx.sync()
-    single_call = time.perf_counter() - t0
-    if dist is not None:
-        import torch
-        t = torch.tensor([single_call], dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        single_call = float(t[0])
+    more_windows, single_call = [], None
+    if args.full:
+        # the same window five more times (the solve keeps running: K further iterations each) -- `value` is the FIRST window, as the contract
+        # says; these show how much one 20-iteration window of ~35 ms scatters
+        if world == 1 and resumed:
+            L.projcg_(x, None, A, U, b, None, tol=1e-300, maxit=W, work=work, n_global=n, want_lambda=False)      # (the norm above ended the first solve)
+            for _ in range(5):
+                ctx.sync(); t0w = time.perf_counter()
+                L.projcg_(x, None, A, U, b, None, tol=1e-300, maxit=K, work=work, n_global=n, want_lambda=False, resume=True)
+                ctx.sync(); more_windows.append(K / (time.perf_counter() - t0w))
+        # the same K iterations as ONE fresh call (set-up inside the clock): what a caller of projcg! with maxit = K sees
+        barrier()
+        t0 = time.perf_counter()
+        L.projcg_(x, None, A, U, b, None, tol=1e-300, maxit=K, work=work, n_global=n, want_lambda=False)
+        ctx.sync()
+        single_call = time.perf_counter() - t0
+        if dist is not None:
+            import torch
+            t = torch.tensor([single_call], dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            single_call = float(t[0])
 
     # ---- per-kernel roofline numbers (HIP events on the library's stream) ---------------
     def avg(slot):
@@ -246,22 +256,6 @@ def main(argv=None, lib=None):
     bytes_k3 = 8.0 * n_loc * m + 32.0 * n_loc + 8.0 * m
     bytes_kf = 8.0 * n_loc * m + 32.0 * n_loc + 8.0 * m
     gbs = lambda by, ms: by / (ms * 1e-3) / 1e9
-    # plain matvecs (the "achieved HBM GB/s on J matvec" half of the metric)
-    v = ctx.vector(n_loc).hash_fill(5, r0)
-    tt = ctx.vector(m).hash_fill(6)
-    y = ctx.vector(n_loc)
-    reps = 5
-    L.gemv_t(Z, v, tt); L.gemv_n(Z, tt, y)
-    ctx.timer_begin()
-    for _ in range(reps):
-        L.gemv_t(Z, v, tt)
-    ms_t = ctx.timer_end() / reps
-    ctx.timer_begin()
-    for _ in range(reps):
-        L.gemv_n(Z, tt, y, 1.0, 1.0)
-    ms_n = ctx.timer_end() / reps
-    bytes_t = 8.0 * n_loc * m + 8.0 * n_loc + 8.0 * m
-    bytes_n = 8.0 * n_loc * m + 16.0 * n_loc + 8.0 * m
 
     out = {
         "metric": "projected-CG iters/sec at n=1e7, m=128 fp64",
@@ -303,9 +297,26 @@ def main(argv=None, lib=None):
                      "K3_proj_dots": {"ms": k3, "GBs": gbs(bytes_k3, k3)},
                      "iteration_algorithmic_GB": (bytes_k1 + bytes_k2 + bytes_k3) / 1e9,
                      "iteration_GBs": (bytes_k1 + bytes_k2 + bytes_k3) * K / elapsed / 1e9}),
-        "matvec": {"gemv_t": {"ms": ms_t, "GBs": gbs(bytes_t, ms_t), "frac": gbs(bytes_t, ms_t) / HBM_PEAK_GBS},
-                   "gemv_n": {"ms": ms_n, "GBs": gbs(bytes_n, ms_n), "frac": gbs(bytes_n, ms_n) / HBM_PEAK_GBS}},
     }
+    if args.full:
+        # plain matvecs (the "achieved HBM GB/s on J matvec" half of the metric)
+        v = ctx.vector(n_loc).hash_fill(5, r0)
+        tt = ctx.vector(m).hash_fill(6)
+        y = ctx.vector(n_loc)
+        reps = 5
+        L.gemv_t(Z, v, tt); L.gemv_n(Z, tt, y)
+        ctx.timer_begin()
+        for _ in range(reps):
+            L.gemv_t(Z, v, tt)
+        ms_t = ctx.timer_end() / reps
+        ctx.timer_begin()
+        for _ in range(reps):
+            L.gemv_n(Z, tt, y, 1.0, 1.0)
+        ms_n = ctx.timer_end() / reps
+        bytes_t = 8.0 * n_loc * m + 8.0 * n_loc + 8.0 * m
+        bytes_n = 8.0 * n_loc * m + 16.0 * n_loc + 8.0 * m
+        out["matvec"] = {"gemv_t": {"ms": ms_t, "GBs": gbs(bytes_t, ms_t), "frac": gbs(bytes_t, ms_t) / HBM_PEAK_GBS},
+                         "gemv_n": {"ms": ms_n, "GBs": gbs(bytes_n, ms_n), "frac": gbs(bytes_n, ms_n) / HBM_PEAK_GBS}}
 
     # HBM traffic of the roofline kernel: PMC counters cannot be read from inside the timed run, they come from separate
     # rocprofv3 --pmc passes of this same command (tools/gpu_final.sh; tools/pmc_summary.py applies the guide's gfx950
@@ -329,9 +340,9 @@ def main(argv=None, lib=None):
     except (OSError, ValueError, KeyError, AttributeError):
         pass
 
-    if not args.no_extras and world == 1:                 # single-GPU diagnostics; the N > 1 runs measure the metric only
+    if args.full and not args.no_extras and world == 1:           # single-GPU diagnostics; the N > 1 runs measure the metric only
         out["extras"] = extras(ctx, L, n, m, n_loc, r0, Z, gbs)
-    if fused:
+    if args.full and fused:
         # what a caller WITHOUT the policy gets: the pair of FIRST allocations of this process is trial (0, 0); its trial time, scaled by
         # (F in the timed run) / (trial time of the kept pair) -- the trial runs on zeros, 2-5 % faster than on data -- estimates its F
         f0 = kf if first_probe is None else first_probe[0] * kf / first_probe[1]
@@ -345,9 +356,10 @@ def main(argv=None, lib=None):
     if more_windows:
         out["further_windows_iters_per_s"] = [round(v, 1) for v in more_windows]
     out["check"] = {"x_norm": x_norm, "nr": nr, "iters": iters}    # global ||x|| after the W + K iterations (sanity / N-rank agreement)
-    out["single_call"] = {"value": K / single_call, "ms_per_step": single_call / K * 1e3,
-                          "note": f"one lfpsqp_projcg call with maxit = {K}: set-up (x = 0, r = -b, U'r, first projection: 2 passes over U) + {K} iterations"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if single_call is not None:
+        out["single_call"] = {"value": K / single_call, "ms_per_step": single_call / K * 1e3,
+                              "note": f"one lfpsqp_projcg call with maxit = {K}: set-up (x = 0, r = -b, U'r, first projection: 2 passes over U) + {K} iterations"}
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(int(args.cpu_sample_n), m, n, args.side_scale)
     if rank == 0:
         print(json.dumps(out))

@@ -1,12 +1,13 @@
 """bench.py's harness logic (argument handling, JSON contract, roofline / cpu_baseline
-objects) exercised at toy size on the emulator build; the numbers mean nothing here."""
+objects, the plain run against --full) exercised at toy size on the emulator build; the numbers mean nothing here."""
 import json
 
 import bench
 
 
 def test_bench_json_contract(emu_lib, capsys):
-    out = bench.main(["--gpus", "1", "--steps", "3", "--warmup", "1", "--rows", "4096", "--cols", "8", "--cpu-sample-n", "4096", "--prewarm-seconds", "0.05", "--side-scale", "0.04"], lib=emu_lib)
+    out = bench.main(["--gpus", "1", "--steps", "3", "--warmup", "1", "--rows", "4096", "--cols", "8", "--cpu-sample-n", "4096", "--prewarm-seconds", "0.05", "--side-scale", "0.04",
+                      "--full"], lib=emu_lib)
     line = capsys.readouterr().out.strip().splitlines()[-1]
     d = json.loads(line)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -24,6 +25,36 @@ def test_bench_json_contract(emu_lib, capsys):
     assert d["roofline"]["traffic"] is None            # no PMC passes of this build
     ops = d["extras"]["operators"]                   # the one-pass iteration with non-diagonal Hessians, timed beside the headline
     assert "error" not in ops and ops["tridiagonal_one_pass_ms"] > 0 and ops["diagonal_plus_rank4_one_pass_ms"] > 0
+
+
+def test_bench_plain_run_measures_the_headline_only(emu_lib, tmp_path, capsys, monkeypatch):
+    """Without --full the run sets up, warms up, times the steps, dumps and prints: the contract keys and the figures of the timed steps, none
+    of the side measurements (CPU baseline, extras, further windows, single call, matvecs) -- and the timed steps and their outputs are the
+    ones a --full run makes."""
+    import numpy as np
+
+    def refused(*a, **k):
+        raise AssertionError("side measurement in a plain run")
+    common = ["--gpus", "1", "--steps", "3", "--warmup", "2", "--rows", "5000", "--cols", "6", "--prewarm-seconds", "0.02", "--cpu-sample-n", "5000",
+              "--side-scale", "0.04"]
+    with monkeypatch.context() as mp:
+        mp.setattr(bench, "cpu_baseline", refused)
+        mp.setattr(bench, "extras", refused)
+        bench.main([*common, "--dump-outputs", str(tmp_path / "plain")], lib=emu_lib)
+    d = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+                "data", "config", "roofline", "kernels", "check"):
+        assert key in d, key
+    for key in ("cpu_baseline", "extras", "further_windows_iters_per_s", "single_call", "matvec", "first_allocation"):
+        assert key not in d, key
+    assert d["steps"] == 3 and d["warmup"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0 and d["check"]["iters"] == 5
+    bench.main([*common, "--full", "--dump-outputs", str(tmp_path / "full")], lib=emu_lib)
+    f = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    for key in ("cpu_baseline", "extras", "further_windows_iters_per_s", "single_call", "matvec", "first_allocation"):
+        assert key in f, key
+    assert f["check"] == d["check"]
+    for name in ("x", "x_rows", "nr", "iters"):
+        np.testing.assert_array_equal(np.load(tmp_path / "plain" / f"{name}.npy"), np.load(tmp_path / "full" / f"{name}.npy"))
 
 
 def test_bench_dump_outputs(emu_lib, tmp_path, capsys):

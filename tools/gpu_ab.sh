@@ -2,7 +2,7 @@
 # A/B of library variants (tools/build_variant.py) on one box: each variant's bench line twice, interleaved.
 #   gpurun -- bash tools/gpu_ab.sh "<extra bench args>" tagA tagB ...     ("main" = the product library)
 mkdir -p gpurun_out/ab
-ARGS="$1"; shift
+ARGS="--full $1"; shift                  # (--full: the matvec timings below)
 for rep in 1 2; do
   for tag in "$@"; do
     lib=""; [ "$tag" != "main" ] && lib="--lib lfpsqp.jl_amd/lib/variants/liblfpsqp_$tag.so"

@@ -3,11 +3,11 @@
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out/final; export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/final
 bash tools/gpu_boxinfo.sh > /dev/null 2>&1; cp gpurun_out/boxinfo.txt $O/boxinfo.txt
 timeout 2400 python -m pytest tests -m gpu -q 2>&1 | tail -12 | tee $O/pytest_gpu.txt
-python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; cat $O/bench.json | cut -c1-600
+python bench.py --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; cat $O/bench.json | cut -c1-600
 cd /tmp
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_profiled.json 2> $O/stats.err
-timeout 900 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -- python3 $R/bench.py --steps 6 --warmup 1 --no-cpu-baseline --no-extras > $O/pmc_fetch.log 2>&1
-timeout 900 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write -- python3 $R/bench.py --steps 6 --warmup 1 --no-cpu-baseline --no-extras > $O/pmc_write.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline > $O/bench_profiled.json 2> $O/stats.err
+timeout 900 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -- python3 $R/bench.py --steps 6 --warmup 1 --full --no-cpu-baseline --no-extras > $O/pmc_fetch.log 2>&1
+timeout 900 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write -- python3 $R/bench.py --steps 6 --warmup 1 --full --no-cpu-baseline --no-extras > $O/pmc_write.log 2>&1
 hipcc --offload-arch=gfx950 -O3 -Wno-unused-result -o /tmp/segprobe $R/tools/micro/segprobe.hip 2>/dev/null
 timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_calib -- /tmp/segprobe > $O/pmc_calib.log 2>&1
 cd $R
