@@ -482,6 +482,24 @@ int lfpsqp_projcg_tridiag(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, co
                           const lfpsqp_projcg_work* work, int64_t* iters, double* nr);
 int lfpsqp_tridiag_mul(lfpsqp_ctx* ctx, const lfpsqp_tridiag_op* A, const lfpsqp_vec* v, lfpsqp_vec* out);
 
+/* ... and for a BANDED Hessian of bandwidth bw = 1 .. 4 (a penalty on second or higher differences -- Whittaker / Hodrick-Prescott smoothing,
+ * curvature terms, discretised 4th-order operators; the reference wraps hess_lag_vec! in a LinearMap, src/optimize.jl:228-230):
+ *     (A v)_i = (a0 + dg_i) v_i + sum_{k=1..bw} ( off_k[i-k] v_{i-k} + off_k[i] v_{i+k} )
+ * off: a plain device matrix (no view) with at least bw columns, column k-1 = off_k; off_k[i] couples rows i and i+k, entries with i + k >= its
+ * number of rows are ignored.  Still ONE pass over U per iteration: the row record of the pass is that of lfpsqp_projcg_tridiag, the vector
+ * kernel before it reads d within 2 bw rows, and U'A U is formed once per solve by one shifted weighted Gram pass per off-diagonal, plus one or
+ * two.  bw = 1 runs the kernels of lfpsqp_projcg_tridiag (the same results, bit for bit).  Av, the basis shapes, the flags, the stacked form (off
+ * of N rows, the x half's couplings; dg stacked) and the refusals (LFPSQP_ERR_UNSUPPORTED: matrix view as basis, fewer than 4 or more than 1024
+ * columns, a communicator, c != 0 with a stacked basis; RESUME / START_PROJECTED are argument errors) are those of lfpsqp_projcg_tridiag;
+ * bw outside 1 .. 4 or a view as off: LFPSQP_ERR_ARG.  Iterates, counts and exits as projcg! with A as a matrix (src/projcg.jl:40-121), to
+ * rounding.
+ * lfpsqp_band_mul: out = A v (out != v), the operator on its own (mul! of the LinearMap); it takes the same stacked pair (v, out stacked, off of
+ * N rows). */
+int lfpsqp_projcg_band(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, double a0, const lfpsqp_vec* dg, const lfpsqp_mat* off, int64_t bw,
+                       lfpsqp_vec* Av, const lfpsqp_basis* U, const lfpsqp_vec* b, const lfpsqp_vec* c, double tol, int64_t maxit,
+                       int64_t n_global, int flags, const lfpsqp_projcg_work* work, int64_t* iters, double* nr);
+int lfpsqp_band_mul(lfpsqp_ctx* ctx, double a0, const lfpsqp_vec* dg, const lfpsqp_mat* off, int64_t bw, const lfpsqp_vec* v, lfpsqp_vec* out);
+
 /* The same solver for a GENERAL symmetric operator A -- the reference's LinearMap closure around hess_lag_vec! /
  * augmented_hess_lag_vec! (src/optimize.jl:228-230, applied at src/projcg.jl:57,74,116): `A(user, src, dest)` must produce
  * dest = A * src for device vectors of length(b) (stacked [x | gap | y] when U is a stacked basis), return 0, and leave

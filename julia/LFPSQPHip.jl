@@ -237,6 +237,10 @@ c_projcg_tridiag(ctx, x, lam, A, Av, U, b, c, tol, maxit, nglob, flags, work, it
     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{CTridiagOp}, Ptr{Cvoid}, Ref{CBasis}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Int64, Int64, Cint, Ref{CWork}, Ref{Int64}, Ref{Float64}),
     ctx, x, lam, A, Av, U, b, c, tol, maxit, nglob, flags, work, iters, nr)
 c_tridiag_mul(ctx, A, v, out) = ccall((:lfpsqp_tridiag_mul, lib), Cint, (Ptr{Cvoid}, Ref{CTridiagOp}, Ptr{Cvoid}, Ptr{Cvoid}), ctx, A, v, out)
+c_projcg_band(ctx, x, lam, a0, dg, off, bw, Av, U, b, c, tol, maxit, nglob, flags, work, iters, nr) = ccall((:lfpsqp_projcg_band, lib), Cint,
+    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ref{CBasis}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Int64, Int64, Cint, Ref{CWork}, Ref{Int64}, Ref{Float64}),
+    ctx, x, lam, a0, dg, off, bw, Av, U, b, c, tol, maxit, nglob, flags, work, iters, nr)
+c_band_mul(ctx, a0, dg, off, bw, v, out) = ccall((:lfpsqp_band_mul, lib), Cint, (Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}), ctx, a0, dg, off, bw, v, out)
 c_projcg_op(ctx, x, lam, A, user, Av, U, b, c, tol, maxit, nglob, flags, work, iters, nr) = ccall((:lfpsqp_projcg_op, lib), Cint,
     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{CBasis}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Int64, Int64, Cint, Ref{CWork}, Ref{Int64}, Ref{Float64}),
     ctx, x, lam, A, user, Av, U, b, c, tol, maxit, nglob, flags, work, iters, nr)
@@ -594,6 +598,20 @@ function LinearAlgebra.mul!(dest::DeviceVector, A::TridiagonalOperator, v::Devic
     return dest
 end
 
+# (A v)_i = (a0 + dg_i) v_i + Σ_{k=1..bw} (off_k[i-k] v_{i-k} + off_k[i] v_{i+k}), 1 <= bw <= 4: couplings up to bw rows apart (second or higher
+# differences).  off: an n x (>= bw) device matrix, column k = off_k (entries with i + k > n are ignored).  projcg! keeps ONE pass over the basis
+# per iteration with it (lfpsqp_projcg_band; bw = 1 is the tridiagonal path); mul! is the LinearMap's action.
+struct BandedOperator
+    a0::Float64
+    dg::Union{Nothing,DeviceVector}
+    off::DeviceMatrix
+    bw::Int
+end
+function LinearAlgebra.mul!(dest::DeviceVector, A::BandedOperator, v::DeviceVector)
+    GC.@preserve A check(dest.ctx, c_band_mul(dest.ctx.h, A.a0, A.dg === nothing ? C_NULL : A.dg.h, A.off.h, Int64(A.bw), v.h, dest.h))
+    return dest
+end
+
 # InequalityData(xl, xu) (src/inequality_helper.jl:39-89), device-resident q, r, s, t
 struct InequalityData
     q::DeviceVector
@@ -728,6 +746,21 @@ function projcg!(x::DeviceVector, λ::Union{Nothing,DeviceVector}, A::Tridiagona
     flags = (λ === nothing ? Cint(0) : LFPSQP_PROJCG_WANT_LAMBDA) | (start_given ? LFPSQP_PROJCG_START_GIVEN : Cint(0))
     rc = GC.@preserve U A c_projcg_tridiag(x.ctx.h, x.h, λ === nothing ? C_NULL : λ.h, Ref(ctridiag(A)), Av.h, Ref(cbasis(U)),
                                            b.h, c === nothing ? C_NULL : c.h, tol, Int64(maxit), Int64(n_global), flags, Ref(cwork(work)), iters, nr)
+    if rc == LFPSQP_ERR_UNSUPPORTED && !start_given
+        return projcg!(x, λ, (dest, src) -> mul!(dest, A, src), U, b, c; tol=tol, maxit=maxit, work=work, n_global=n_global)
+    end
+    check(x.ctx, rc)
+    return Int(iters[]), nr[]
+end
+# Banded Hessian: the same rules as the tridiagonal one (lfpsqp_projcg_band; A.off has N rows with a stacked basis)
+function projcg!(x::DeviceVector, λ::Union{Nothing,DeviceVector}, A::BandedOperator, U::AnyBasis, b::DeviceVector, c::Union{Nothing,DeviceVector};
+                 tol::Float64=1e-6, maxit::Int=length(b) + ncols(U), work::ProjCGWork=ProjCGWork(x, ncols(U)), n_global::Int=length(b),
+                 Av::DeviceVector=DeviceVector(x.ctx, length(b)), start_given::Bool=false)
+    iters = Ref{Int64}(0); nr = Ref{Float64}(0.0)
+    flags = (λ === nothing ? Cint(0) : LFPSQP_PROJCG_WANT_LAMBDA) | (start_given ? LFPSQP_PROJCG_START_GIVEN : Cint(0))
+    rc = GC.@preserve U A c_projcg_band(x.ctx.h, x.h, λ === nothing ? C_NULL : λ.h, A.a0, A.dg === nothing ? C_NULL : A.dg.h, A.off.h, Int64(A.bw),
+                                        Av.h, Ref(cbasis(U)), b.h, c === nothing ? C_NULL : c.h, tol, Int64(maxit), Int64(n_global), flags,
+                                        Ref(cwork(work)), iters, nr)
     if rc == LFPSQP_ERR_UNSUPPORTED && !start_given
         return projcg!(x, λ, (dest, src) -> mul!(dest, A, src), U, b, c; tol=tol, maxit=maxit, work=work, n_global=n_global)
     end
@@ -1386,6 +1419,9 @@ scalar_hessian(h) = false      # true: grad^2 of the Lagrangian is a multiple of
 # A TRIDIAGONAL Lagrangian Hessian: hess_diag! fills the diagonal, hess_offdiag(problem) returns the device vector of the couplings (entry i couples
 # variables i and i+1) or nothing.  The truncated-Newton solves then run projcg! with a TridiagonalOperator: one pass per iteration.
 hess_offdiag(h) = nothing
+# A BANDED one (bandwidth 2 .. 4): hess_band(problem) returns an N x bw device matrix (column k couples variables i and i+k) or nothing; the
+# truncated-Newton solves then run projcg! with a BandedOperator under the same rules.
+hess_band(h) = nothing
 
 function optimize_core(ctx::HipContext, f, grad!, c!, jac!, hess_lag_vec!, x0::Vector{Float64}, xl, xu, m::Int, param::LFPSQPParams=LFPSQPParams();
                        n_global::Int=length(x0))
@@ -1424,7 +1460,7 @@ function optimize_core(ctx::HipContext, f, grad!, c!, jac!, hess_lag_vec!, x0::V
     # (the library says whether this context can run projcg! without Z for this Jct: one-pass kernels on, shape inside their limits, or a
     # sparse twin the nonzero path covers; otherwise Z is materialised and every path has its two-pass form)
     # (a tridiagonal Hessian sent through the callback path -- DeviceOptions.tridiagonal_one_pass off -- needs the materialised basis)
-    tri_callback = diagonal_hessian && hess_offdiag(hess_lag_vec!) !== nothing && !ctx.options.tridiagonal_one_pass
+    tri_callback = diagonal_hessian && (hess_offdiag(hess_lag_vec!) !== nothing || hess_band(hess_lag_vec!) !== nothing) && !ctx.options.tridiagonal_one_pass
     factored_basis = ctx.options.factored_basis && diagonal_hessian && !tri_callback && 4 <= m <= 1024 && factored_basis_supported(ctx, Jct, jsp === nothing ? C_NULL : jsp.h)
     # allocation by trial pays after several hundred projected-CG iterations; a Lagrangian Hessian that is a multiple of I (config 3) ends every
     # truncated-Newton solve after one: such a run takes its first allocations
@@ -1452,7 +1488,8 @@ function optimize_core(ctx::HipContext, f, grad!, c!, jac!, hess_lag_vec!, x0::V
     nonlinear_class = c! isa DeviceConstraints && c!.ew !== nothing          # (its Jct may be a view of A, its Hessian term may need A*λ)
     fuse_tangent = factored_basis && param.do_newton && jsp === nothing && m > 0 && ctx.options.fused_tangent_step && !(ineq && nonlinear_class)
     tri_off = diagonal_hessian ? hess_offdiag(hess_lag_vec!) : nothing
-    if tri_off !== nothing                                    # (with bounds: the augmented stacked diagonal next to the same couplings)
+    band_off = (diagonal_hessian && tri_off === nothing) ? hess_band(hess_lag_vec!) : nothing
+    if tri_off !== nothing || band_off !== nothing           # (with bounds: the augmented stacked diagonal next to the same couplings)
         ctx.options.tridiagonal_one_pass || (fuse_tangent = false)     # (the callback path starts its solves itself)
         (haskey(VIEW_KEEP, Jct) || ctx.nranks > 1) && (fuse_tangent = false)  # (lfpsqp_projcg_tridiag refuses a matrix view / several ranks: callback path, its own start)
     end                                                       # (the tangent step still hands projcg! r0 and U'r0; never its folded initial projection)
@@ -1548,7 +1585,7 @@ function optimize_core(ctx::HipContext, f, grad!, c!, jac!, hess_lag_vec!, x0::V
                     hess_diag!(hess_lag_vec!, hdst, x, λ_kkt)
                 end
                 # the fold of projcg!'s initial projection: only where the Gram matrix resolves I - U'U (full rank, cond^2 <= 10)
-                init_fold = tri_off === nothing && rank == m && Σ[1]^2 <= 10.0 * Σ[m]^2
+                init_fold = tri_off === nothing && band_off === nothing && rank == m && Σ[1]^2 <= 10.0 * Σ[m]^2
                 GC.@preserve Ub cons_part begin
                     cref = cons_part === nothing ? nothing : Ref(ccons(cons_part))
                     iref = ineq ? Ref(cineq(idata)) : nothing
@@ -1614,6 +1651,15 @@ function optimize_core(ctx::HipContext, f, grad!, c!, jac!, hess_lag_vec!, x0::V
                 elseif tri_off !== nothing
                     tn_iter, tn_res = projcg!(newton_d, nothing, TridiagonalOperator(0.0, a_diag, tri_off), Qview, d, nothing; tol=tol, maxit=param.tn_maxiter,
                                               work=projcgwork, n_global=nglob, start_given=fused_now)
+                elseif band_off !== nothing
+                    Aband = BandedOperator(0.0, a_diag, band_off, band_off.m)
+                    if ctx.options.tridiagonal_one_pass
+                        tn_iter, tn_res = projcg!(newton_d, nothing, Aband, Qview, d, nothing; tol=tol, maxit=param.tn_maxiter,
+                                                  work=projcgwork, n_global=nglob, start_given=fused_now)
+                    else
+                        tn_iter, tn_res = projcg!(newton_d, nothing, (dest, src) -> mul!(dest, Aband, src), Qview, d, nothing; tol=tol,
+                                                  maxit=param.tn_maxiter, work=projcgwork, n_global=nglob)
+                    end
                 else
                     tn_iter, tn_res = projcg!(newton_d, nothing, DiagOperator(0.0, a_diag), Qview, d, nothing; tol=tol, maxit=param.tn_maxiter,
                                               work=projcgwork, n_global=nglob, start_projected=fused_now && init_fold, start_given=fused_now && !init_fold)
@@ -1777,24 +1823,47 @@ function optimize(P::SeparableLinearBallBox, x0::Vector{Float64}, param::LFPSQPP
     return x[1:B.n], obj, λ, info
 end
 
-# ---- separable objective plus a CHAIN term: f(x) = Σ φ(x_i - c_i; a_i) + κ/2 Σ_{i<n} (x_{i+1} - x_i)² under dense linear equalities ----------------
-# (the kind of objective whose Hessian the reference reaches only through hess_lag_vec!, src/autodiff_generators.jl:72-107).  The Lagrangian
-# Hessian is TRIDIAGONAL: diagonal φ''(x_i) + κ deg_i (deg = 1 at the two ends, 2 inside), couplings -κ.  optimize_core finds the couplings
-# through hess_offdiag and runs its truncated-Newton solves on the one-pass solver (lfpsqp_projcg_tridiag).  One rank, no ball, no bounds.
+# ---- separable objective plus a CHAIN term: f(x) = Σ φ(x_i - c_i; a_i) + κ/2 ‖Δ^r x‖² under dense linear equalities -------------------------------
+# (Δ^r the r-th forward difference, order r = 1 .. 4; r = 1: κ/2 Σ_{i<n} (x_{i+1} - x_i)²; the kind of objective whose Hessian the reference
+# reaches only through hess_lag_vec!, src/autodiff_generators.jl:72-107).  r = 1: the Lagrangian Hessian is TRIDIAGONAL: diagonal φ''(x_i) + κ
+# deg_i (deg = 1 at the two ends, 2 inside), couplings -κ; optimize_core finds them through hess_offdiag (lfpsqp_projcg_tridiag).  r >= 2: it is
+# BANDED, the diagonal and the r off-diagonals of κ Δ^r'Δ^r built once on the host; optimize_core finds them through hess_band
+# (lfpsqp_projcg_band).  One rank, no ball, no bounds.
 struct ChainSeparableLinear
     sep::SeparableLinearBallBox
     κ::Float64
-    deg::DeviceVector           # κ .* degree of the path graph
-    off::DeviceVector           # -κ (entry n is ignored)
+    order::Int
+    deg::DeviceVector                   # the diagonal of κ Δ^r'Δ^r (r = 1: κ .* degree of the path graph)
+    off::Union{Nothing,DeviceVector}    # r = 1: -κ (entry n is ignored)
+    offs::Union{Nothing,DeviceMatrix}   # r >= 2: n x r, column k = the k-th off-diagonal (its last k entries zero)
     tmp::DeviceVector
 end
-function ChainSeparableLinear(ctx::HipContext, n::Int, m::Int, Jct::DeviceMatrix, b::Vector{Float64}, kind::Int, a::Vector{Float64}, c::Vector{Float64}; κ::Float64=1.0)
-    ctx.nranks == 1 || error("chain objective: one rank (the couplings would cross the shard boundaries)")
-    sep = SeparableLinearBallBox(ctx, n, m, Jct, b, kind, a, c)
-    deg = fill(2.0 * κ, n); deg[1] = deg[n] = n > 1 ? κ : 0.0
-    return ChainSeparableLinear(sep, κ, upload!(DeviceVector(ctx, n), deg), upload!(DeviceVector(ctx, n), fill(-κ, n)), DeviceVector(ctx, n))
+function difference_band(n::Int, order::Int, κ::Float64)
+    cf = [(-1.0)^(order - t) * binomial(order, t) for t in 0:order]      # row j of Δ^r: cf[t+1] at column j + t
+    rows = max(n - order, 0)
+    dg = zeros(n); off = zeros(n, order)
+    for t in 0:order
+        dg[t+1:t+rows] .+= cf[t+1]^2
+        for k in 1:order-t
+            off[t+1:t+rows, k] .+= cf[t+1] * cf[t+k+1]
+        end
+    end
+    return κ .* dg, κ .* off
 end
-laplacian(P::ChainSeparableLinear) = TridiagonalOperator(0.0, P.deg, P.off)         # κ L, L = the path graph's Laplacian
+function ChainSeparableLinear(ctx::HipContext, n::Int, m::Int, Jct::DeviceMatrix, b::Vector{Float64}, kind::Int, a::Vector{Float64}, c::Vector{Float64};
+                              κ::Float64=1.0, order::Int=1)
+    ctx.nranks == 1 || error("chain objective: one rank (the couplings would cross the shard boundaries)")
+    1 <= order <= 4 || error("chain objective: order 1 .. 4")
+    sep = SeparableLinearBallBox(ctx, n, m, Jct, b, kind, a, c)
+    if order == 1
+        deg = fill(2.0 * κ, n); deg[1] = deg[n] = n > 1 ? κ : 0.0
+        return ChainSeparableLinear(sep, κ, 1, upload!(DeviceVector(ctx, n), deg), upload!(DeviceVector(ctx, n), fill(-κ, n)), nothing, DeviceVector(ctx, n))
+    end
+    deg, offs = difference_band(n, order, κ)
+    return ChainSeparableLinear(sep, κ, order, upload!(DeviceVector(ctx, n), deg), nothing, upload!(DeviceMatrix(ctx, n, order), offs), DeviceVector(ctx, n))
+end
+laplacian(P::ChainSeparableLinear) = P.order == 1 ? TridiagonalOperator(0.0, P.deg, P.off) :   # κ L, L = the path graph's Laplacian
+                                     BandedOperator(0.0, P.deg, P.offs, P.order)                 # κ Δ^r'Δ^r
 function objective(P::ChainSeparableLinear, x::DeviceVector)
     mul!(P.tmp, laplacian(P), x)
     return objective(P.sep, x) + 0.5 * dot(x, P.tmp)
@@ -1817,6 +1886,7 @@ function hess_diag_objective!(P::ChainSeparableLinear, hx::DeviceVector, x::Devi
 end
 hess_constraints(P::ChainSeparableLinear) = P.sep.base.cons
 hess_offdiag(P::ChainSeparableLinear) = P.off
+hess_band(P::ChainSeparableLinear) = P.offs
 function optimize(P::ChainSeparableLinear, x0::Vector{Float64}, param::LFPSQPParams=LFPSQPParams())
     B = P.sep.base
     x, obj, λ, info = optimize_core(B.ctx, x -> objective(P, x), (g, x) -> gradient!(P, g, x), B.cons, (J, cv, x) -> jac!(B.cons, J, cv, x), P,
@@ -1922,7 +1992,7 @@ optimize(ctx::HipContext, f, grad!, c!, jac_c!, d!, jac_d!, hess_lag_vec!, x0::V
 
 export HipContext, HipError, DeviceOptions, DeviceVector, StackedVector, DeviceMatrix, SparseMatrix, spmv_t!, spmv_n!, to_dense!, DeviceBasis, DiagOperator, LowRankOperator, InequalityData, InequalityDecomp,
        InequalityDecompProject, ProjCGWork, DeviceConstraints, NR, ProjPenalty, ProjPenaltyWork, Euclidean, YRetract, ArmijoWork,
-       ExactLinesearchWork, LFPSQPParams, TerminationInfo, QuadLinearBallBox, SeparableLinearBallBox, ChainSeparableLinear, TridiagonalOperator, SeparableElementwiseBox, ElementwiseConstraints,
+       ExactLinesearchWork, LFPSQPParams, TerminationInfo, QuadLinearBallBox, SeparableLinearBallBox, ChainSeparableLinear, TridiagonalOperator, BandedOperator, SeparableElementwiseBox, ElementwiseConstraints,
        sin_system_constraints, sphere_system_constraints, clone, rowscale!, set_placement!, basis_and_vectors_placed, vectors_placed, placement_info, upload!, download, upload2!, download2, projcg!, retract!,
        retract_nr_batch!, pcg!, ProjPrecondition, ksvd!, armijo!, exact_linesearch!, optimize, optimize_core, hess_diag!, jac!, comm_unique_id, comm_init!, comm_p2p_export, comm_init_p2p!,
        shard_range, sync

@@ -173,6 +173,9 @@ _SIGS = {
     "lfpsqp_projcg_tridiag": [P, P, P, C.POINTER(TridiagOp), P, C.POINTER(Basis), P, P, c_dbl, c_i64, c_i64, C.c_int,
                               C.POINTER(ProjCGWorkC), C.POINTER(c_i64), PD],
     "lfpsqp_tridiag_mul": [P, C.POINTER(TridiagOp), P, P],
+    "lfpsqp_projcg_band": [P, P, P, c_dbl, P, P, c_i64, P, C.POINTER(Basis), P, P, c_dbl, c_i64, c_i64, C.c_int,
+                           C.POINTER(ProjCGWorkC), C.POINTER(c_i64), PD],
+    "lfpsqp_band_mul": [P, c_dbl, P, P, c_i64, P, P],
     "lfpsqp_projcg_op": [P, P, P, P, P, P, C.POINTER(Basis), P, P, c_dbl, c_i64, c_i64, C.c_int,
                          C.POINTER(ProjCGWorkC), C.POINTER(c_i64), PD],
     "lfpsqp_ctx_stream": [P, C.POINTER(P)],

@@ -44,15 +44,17 @@ constexpr int kTLd = 17;
 // is an operand of npan - 1 off-diagonal pairs), so they are placed on the SAME XCD, next to each other in dispatch order
 // (linear workgroup id L -> XCD L % 8): the panels then come from HBM once and from that XCD's L2 for the other pairs.  With
 // the pair as the slow grid dimension (one pair after the other) the m = 512 Gram read 61 GB for a 20 GB matrix.
-// SHIFT (weighted launches only): the operand is not M but R with rows R_i = M_i + sgn_i M_{i+1} (sgn_i = +-1; M_n = 0), formed in registers
-// on the way to LDS -- one more scalar load per column and step (the row below a lane's pair; same cache line but for one lane in eight).
-// This is the Gram matrix behind the reduced operator of a tridiagonal Hessian (lfpsqp_projcg_tridiag: U'A U = R'|off| R + U' diag(c) U).
-template <bool DIAG, bool WEIGHTED, bool SHIFT = false, int NX = 0>
+// SHIFT = k > 0 (weighted launches only): the operand is not M but R with rows R_i = M_i + sgn_i M_{i+k} (sgn_i = +-1; M_j = 0 for j >= n, k <= 4),
+// formed in registers on the way to LDS.  k = 1: one more scalar load per column and step (the row below a lane's pair; same cache line but for one
+// lane in eight); k even: one aligned pair load of rows kh + k, kh + k + 1; k odd > 1: two scalar loads.  This is the Gram matrix behind the
+// reduced operator of a banded Hessian (lfpsqp_projcg_tridiag / lfpsqp_projcg_band: U'A U = sum_k R_k'|off_k| R_k + U' diag(c) U).
+template <bool DIAG, bool WEIGHTED, int SHIFT = 0, int NX = 0>
 __global__ __launch_bounds__(kThreads, 2) void gram_kernel(const double* __restrict__ M, int64_t ld, int64_t n, int ncols, int npan,
                                                          int ngroups, const double* __restrict__ w2, double* __restrict__ part,
                                                          int64_t part_ld, const double* __restrict__ ex0, const double* __restrict__ ex1,
                                                          int64_t xoff, const double* __restrict__ sgn) {
-    static_assert(!SHIFT || WEIGHTED, "the shifted operand exists for weighted launches only");
+    static_assert(SHIFT == 0 || WEIGHTED, "the shifted operand exists for weighted launches only");
+    static_assert(SHIFT >= 0 && SHIFT <= 4, "shift distances 1 .. 4");
     // NX: how many of the extra right-hand columns (ex0, then ex1) this launch carries -- a compile-time fact: as run-time null tests of two
     // pointers the columns' multiply-adds were if-converted into 32 FMAs and ~37 compares / selects per two steps of EVERY launch, more vector
     // instructions than the rest of the loop has, between the matrix-core instructions of a wave (FINDINGS.md 12.8)
@@ -91,7 +93,9 @@ __global__ __launch_bounds__(kThreads, 2) void gram_kernel(const double* __restr
     // software pipeline: the global loads of step s+DEPTH are issued before the MFMAs of step s.  Row weights are applied when a
     // buffer is staged, so that no arithmetic waits on the loads in flight.
     double2 va[DEPTH][4], vb[needB ? DEPTH : 1][4], vw[WEIGHTED ? DEPTH : 1];
-    double za[SHIFT ? DEPTH : 1][SHIFT ? 4 : 1], zb[(SHIFT && needB) ? DEPTH : 1][(SHIFT && needB) ? 4 : 1];     // SHIFT: row kh + 2 of the columns
+    // SHIFT: the partner rows of the columns -- k = 1: row kh + 2 (row kh + 1 is the pair's own); else rows kh + k, kh + k + 1
+    using ZT = std::conditional_t<(SHIFT > 1), double2, double>;
+    ZT za[SHIFT ? DEPTH : 1][SHIFT ? 4 : 1], zb[(SHIFT && needB) ? DEPTH : 1][(SHIFT && needB) ? 4 : 1];
     double2 vs[SHIFT ? DEPTH : 1];
     double2 ve[2] = {make_double2(0.0, 0.0), make_double2(0.0, 0.0)};      // the extra columns' entries of the rows kh, kh + 1 of the step in flight
     double xa[2][4] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};         // ... and this lane's running sums for its four panel columns
@@ -129,7 +133,7 @@ __global__ __launch_bounds__(kThreads, 2) void gram_kernel(const double* __restr
             if constexpr (NX > 0) ve[0] = ld2(ex0 + r + kh);
             if constexpr (NX > 1) ve[1] = ld2(ex1 + r + kh);
         }
-        if constexpr (SHIFT) {
+        if constexpr (SHIFT == 1) {
             vs[buf] = ld2(sgn + r + kh);
             const bool below = r + kh + 2 < n;       // (the row below the last one is zero by definition -- and may lie outside the allocation)
 #pragma unroll
@@ -141,13 +145,35 @@ __global__ __launch_bounds__(kThreads, 2) void gram_kernel(const double* __restr
                     if (below && (FULL || 32 * q < nb)) zb[buf][q] = pb[r + q * cs + 2];
                 }
             }
+        } else if constexpr (SHIFT > 1) {
+            vs[buf] = ld2(sgn + r + kh);
+            // rows kh + k, kh + k + 1: zero from row n on (and there may lie outside the allocation); the pair load where both exist
+            const bool b1 = r + kh + SHIFT < n, b2 = r + kh + SHIFT + 1 < n;
+            auto partner = [&](const double* p) -> double2 {
+                if constexpr (SHIFT % 2 == 0) {
+                    if (b2) return ld2(p + SHIFT);
+                    return make_double2(b1 ? p[SHIFT] : 0.0, 0.0);
+                } else {
+                    return make_double2(b1 ? p[SHIFT] : 0.0, b2 ? p[SHIFT + 1] : 0.0);
+                }
+            };
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                za[buf][q] = make_double2(0.0, 0.0);
+                if (FULL || 32 * q < na) za[buf][q] = partner(pa + r + q * cs);
+                if constexpr (needB) {
+                    zb[buf][q] = make_double2(0.0, 0.0);
+                    if (FULL || 32 * q < nb) zb[buf][q] = partner(pb + r + q * cs);
+                }
+            }
         }
     };
     auto write_lds = [&](int p, int buf) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             double2 a = va[buf][q];
-            if constexpr (SHIFT) a = make_double2(fma(vs[buf].x, a.y, a.x), fma(vs[buf].y, za[buf][q], a.y));
+            if constexpr (SHIFT == 1) a = make_double2(fma(vs[buf].x, a.y, a.x), fma(vs[buf].y, za[buf][q], a.y));
+            if constexpr (SHIFT > 1) a = make_double2(fma(vs[buf].x, za[buf][q].x, a.x), fma(vs[buf].y, za[buf][q].y, a.y));
             if constexpr (WEIGHTED) { a.x *= vw[buf].x; a.y *= vw[buf].y; }
             As[p][c + 32 * q][kh] = a.x;
             As[p][c + 32 * q][kh + 1] = a.y;
@@ -157,7 +183,8 @@ __global__ __launch_bounds__(kThreads, 2) void gram_kernel(const double* __restr
             }
             if constexpr (needB) {
                 double2 b = vb[buf][q];
-                if constexpr (SHIFT) b = make_double2(fma(vs[buf].x, b.y, b.x), fma(vs[buf].y, zb[buf][q], b.y));
+                if constexpr (SHIFT == 1) b = make_double2(fma(vs[buf].x, b.y, b.x), fma(vs[buf].y, zb[buf][q], b.y));
+                if constexpr (SHIFT > 1) b = make_double2(fma(vs[buf].x, zb[buf][q].x, b.x), fma(vs[buf].y, zb[buf][q].y, b.y));
                 if constexpr (WEIGHTED) { b.x *= vw[buf].x; b.y *= vw[buf].y; }
                 Bs[p][c + 32 * q][kh] = b.x;
                 Bs[p][c + 32 * q][kh + 1] = b.y;
@@ -619,9 +646,10 @@ struct SqrtWTimesV {
 };
 
 static int gram_impl(lfpsqp_ctx* ctx, const lfpsqp_mat* M, int ncols_all, const double* w2, std::vector<double>& G, const GramRhs* rhs = nullptr,
-                     const double* shift_sgn = nullptr) {
-    // shift_sgn != NULL: the Gram matrix of R, R_i = M_i + shift_sgn_i M_{i+1} (gram_kernel SHIFT) -- plain matrix, weights given, no extra columns
-    if (shift_sgn && (M->view || !w2 || rhs)) return set_err(ctx, LFPSQP_ERR_ARG, "shifted Gram matrix: plain matrix with weights, no right-hand columns");
+                     const double* shift_sgn = nullptr, int shift = 1) {
+    // shift_sgn != NULL: the Gram matrix of R, R_i = M_i + shift_sgn_i M_{i+shift} (gram_kernel SHIFT) -- plain matrix, weights given, no extra columns
+    if (shift_sgn && (M->view || !w2 || rhs || shift < 1 || shift > 4))
+        return set_err(ctx, LFPSQP_ERR_ARG, "shifted Gram matrix: plain matrix with weights, no right-hand columns, shift 1 .. 4");
     G.assign((size_t)ncols_all * ncols_all, 0.0);
     const int nxu = rhs ? rhs->nx : 0;
     if (rhs && rhs->X) rhs->X->assign((size_t)ncols_all * nxu, 0.0);
@@ -743,9 +771,18 @@ static int gram_impl(lfpsqp_ctx* ctx, const lfpsqp_mat* M, int ncols_all, const 
         LF_TRY((run_vec<SqrtWeightF, 0, NoPost>(ctx, M->n, SqrtWeightF{w2, sw}, 0u, nullptr, NoPost())));
         LF_TRY(ensure_part(ctx, (size_t)std::max(gd, go) * pld));         // (run_vec may not shrink it, but keep the reservation next to its use)
         if (shift_sgn) {
-            hipLaunchKernelGGL((gram_kernel<true, true, true>), dim3(gd * npan), dim3(kThreads), 0, ctx->stream, M->p, M->ld, M->n, ncols, npan, gd, sw, ctx->part, pld, nullptr, nullptr, pp, shift_sgn);
-            if (noff > 0)
-                hipLaunchKernelGGL((gram_kernel<false, true, true>), dim3(go * noff), dim3(kThreads), 0, ctx->stream, M->p, M->ld, M->n, ncols, npan, go, sw, ctx->part, pld, nullptr, nullptr, pp, shift_sgn);
+            auto launch_shifted = [&](auto Kc) {
+                constexpr int K = decltype(Kc)::value;
+                hipLaunchKernelGGL((gram_kernel<true, true, K>), dim3(gd * npan), dim3(kThreads), 0, ctx->stream, M->p, M->ld, M->n, ncols, npan, gd, sw, ctx->part, pld, nullptr, nullptr, pp, shift_sgn);
+                if (noff > 0)
+                    hipLaunchKernelGGL((gram_kernel<false, true, K>), dim3(go * noff), dim3(kThreads), 0, ctx->stream, M->p, M->ld, M->n, ncols, npan, go, sw, ctx->part, pld, nullptr, nullptr, pp, shift_sgn);
+            };
+            switch (shift) {
+                case 1: launch_shifted(std::integral_constant<int, 1>{}); break;
+                case 2: launch_shifted(std::integral_constant<int, 2>{}); break;
+                case 3: launch_shifted(std::integral_constant<int, 3>{}); break;
+                default: launch_shifted(std::integral_constant<int, 4>{}); break;
+            }
         } else {
             if (nslots == 2) hipLaunchKernelGGL((gram_kernel<true, true, false, 2>), dim3(gd * npan), dim3(kThreads), 0, ctx->stream, M->p, M->ld, M->n, ncols, npan, gd, sw, ctx->part, pld, ex0, ex1, pp, nullptr);
             else if (nslots == 1) hipLaunchKernelGGL((gram_kernel<true, true, false, 1>), dim3(gd * npan), dim3(kThreads), 0, ctx->stream, M->p, M->ld, M->n, ncols, npan, gd, sw, ctx->part, pld, ex0, ex1, pp, nullptr);
@@ -1275,9 +1312,9 @@ static int check_weights(lfpsqp_ctx* ctx, bool weighted, const std::vector<doubl
     return 0;
 }
 
-// G (ncols x ncols, column-major) = R' diag(w) R for R_i = M_i + sgn_i M_{i+1} (w >= 0 and sgn = +-1: device n-vectors; projcg.hip)
-int lfpsqp::gram_shifted(lfpsqp_ctx* ctx, const lfpsqp_mat* M, int ncols, const double* w, const double* sgn, std::vector<double>& G) {
-    LF_TRY(gram_impl(ctx, M, ncols, w, G, nullptr, sgn));
+// G (ncols x ncols, column-major) = R' diag(w) R for R_i = M_i + sgn_i M_{i+shift} (w >= 0 and sgn = +-1: device n-vectors; projcg.hip)
+int lfpsqp::gram_shifted(lfpsqp_ctx* ctx, const lfpsqp_mat* M, int ncols, const double* w, const double* sgn, std::vector<double>& G, int shift) {
+    LF_TRY(gram_impl(ctx, M, ncols, w, G, nullptr, sgn, shift));
     return check_weights(ctx, true, G);
 }
 

@@ -87,117 +87,162 @@ struct AOpLR {  // A = a0*I + diag(dg) + V diag(sigma) V': (A v)_i = (a0 + dg_i)
     }
 };
 
-// A = a0*I + diag(dg) + tridiagonal couplings: (A v)_i = (a0 + dg_i) v_i + off_{i-1} v_{i-1} + off_i v_{i+1}  (off_i couples rows i and i+1; off_{n-1}
-// is ignored).  lfpsqp_projcg_tridiag / lfpsqp_tridiag_mul.  Stacked (bound-constrained) vectors [x | gap | y]: the couplings act on the first nc
-// rows (the x half, off of length nc), every other row is diagonal -- the Newton map blockdiag(T + diag, diag) of src/inequality_helper.jl:144-158.
-struct TriD {
+// A = a0*I + diag(dg) + banded couplings of bandwidth B (1 .. 4):
+//     (A v)_i = (a0 + dg_i) v_i + sum_{k=1..B} ( off_k[i-k] v_{i-k} + off_k[i] v_{i+k} )
+// (off_k[i] couples rows i and i + k; entries with i + k >= nc are ignored).  B = 1 is the tridiagonal operator of lfpsqp_projcg_tridiag /
+// lfpsqp_tridiag_mul, B > 1 the banded one of lfpsqp_projcg_band / lfpsqp_band_mul.  Stacked (bound-constrained) vectors [x | gap | y]: the
+// couplings act on the first nc rows (the x half, couplings of length nc), every other row is diagonal -- the Newton map blockdiag(T + diag, diag)
+// of src/inequality_helper.jl:144-158.
+template <int B>
+struct BandD {
+    static_assert(B >= 1 && B <= 4, "bandwidth 1 .. 4");
     double a0;
     const double* dg;
-    const double* off;
+    const double* off;        // coupling column k (1 .. B) at off + (k - 1) * ldo (ldo even: pair loads stay aligned)
+    int64_t ldo;
     int64_t n;
     int64_t nc;               // rows with couplings: n, or N of a stacked vector (n = half stride + N)
+    __device__ __forceinline__ const double* col(int k) const { return off + (int64_t)(k - 1) * ldo; }
 };
-struct TriMulF {   // out = A v (a plain vector kernel: the neighbours come out of the cache lines the row itself brings in)
-    TriD A;
+template <int B>
+struct TriMulF {   // out = A v (a plain vector kernel: the neighbours come out of the cache lines the rows themselves bring in)
+    BandD<B> A;
     const double* v;
     double* out;
     const int64_t* istat;     // nullptr: always; else only while the solve is running
     __device__ __forceinline__ bool skip() const { return istat != nullptr && ld_stat(istat + I_STATUS) != ST_RUNNING; }
+    // row j: the diagonal term, then per distance k = 1 .. B the lower and the upper coupling (one fma each); rows >= nc have none
+    __device__ __forceinline__ double row(int64_t j, double vj, double dj) const {
+        double o = (A.a0 + dj) * vj;
+        if (j >= A.nc) return o;
+#pragma unroll
+        for (int k = 1; k <= B; ++k) {
+            const double* ok = A.col(k);
+            const bool lo = j >= k;
+            o = fma(lo ? ok[j - k] : 0.0, lo ? v[j - k] : 0.0, o);
+            if (j + k < A.nc) o = fma(ok[j], v[j + k], o);
+        }
+        return o;
+    }
     __device__ __forceinline__ void apply(int64_t i, bool v0, bool v1, double*) const {
         if (!v0) return;
         const double2 vv = ld2(v + i);
         const double2 dd = A.dg ? ld2(A.dg + i) : make_double2(0.0, 0.0);
-        if (i + 1 >= A.nc && A.nc < A.n) {                 // stacked: the last x row (no coupling to the gap), the gap and the y half
-            double o0 = (A.a0 + dd.x) * vv.x;
-            if (i < A.nc && i > 0) o0 = fma(A.off[i - 1], v[i - 1], o0);
-            if (!v1) { out[i] = o0; return; }
-            st2(out + i, make_double2(o0, (A.a0 + dd.y) * vv.y));
-            return;
-        }
-        const double2 of = ld2(A.off + i);
-        const double vm = (i > 0) ? v[i - 1] : 0.0, om = (i > 0) ? A.off[i - 1] : 0.0;
-        double o0 = fma(om, vm, (A.a0 + dd.x) * vv.x);
-        if (v1) o0 = fma(of.x, vv.y, o0);
+        const double o0 = row(i, vv.x, dd.x);
         if (!v1) { out[i] = o0; return; }
-        double o1 = fma(of.x, vv.x, (A.a0 + dd.y) * vv.y);
-        if (i + 2 < A.nc) o1 = fma(of.y, v[i + 2], o1);
-        st2(out + i, make_double2(o0, o1));
+        st2(out + i, make_double2(o0, row(i + 1, vv.y, dd.y)));
     }
 };
 
-// What the fused tridiagonal iteration (PcgFuseTri) needs from the rows' NEIGHBOURS, as two stored vectors, so that the pass itself is row-local
-// and may update the residual in place:  ad = A d  and  q_i = off_{i-1} rr_{i-1} + off_i rr_{i+1}  with  rr = g + alpha ad  (the off-diagonal part
-// of A rr).  INIT: rr is the stored initial residual (alpha = 0, no direction yet), only q is written.  A vector kernel: six streams of n doubles.
-template <bool INIT>
+// The rows i - 2B .. i + 2B + 1 around a thread's pair (i even) that the preparation kernels below read: window entry t is row i - 2B + t.
+// The thread's rows are t = 2B, 2B + 1; rr (and A d) is needed at t = B .. 3B + 1, d at every t, off_k at t = B - k .. 3B + 1.
+template <int B>
+struct BandWin {
+    static constexpr int W = 4 * B + 2;
+    static constexpr int L = B, H = 3 * B + 1;    // the rows of rr
+    // interior: aligned pair loads (i - 2B is even); a pair none of whose entries is used is dropped by the compiler
+    static __device__ __forceinline__ void pairs(const double* v, int64_t i, double (&o)[W]) {
+#pragma unroll
+        for (int p = 0; p < W / 2; ++p) {
+            const double2 x = ld2(v + i - 2 * B + 2 * p);
+            o[2 * p] = x.x;
+            o[2 * p + 1] = x.y;
+        }
+    }
+};
+
+// What the fused banded iteration (PcgFuseTri) needs from the rows' NEIGHBOURS, as two stored vectors, so that the pass itself is row-local
+// and may update the residual in place:  ad = A d  and  q_i = sum_k (off_k[i-k] rr_{i-k} + off_k[i] rr_{i+k})  with  rr = g + alpha ad  (the
+// off-diagonal part of A rr).  INIT: rr is the stored initial residual (alpha = 0, no direction yet), only q is written.  A vector kernel: for
+// B = 1 six streams of n doubles; every further distance adds one coupling stream (the neighbours' rows come from lines already in the cache).
+// Every small array has a fixed size and is indexed by unrolled constants only: registers, no scratch.
+template <int B, bool INIT>
 struct TriPrepF {
-    TriD A;
+    BandD<B> A;
     const double* g;          // the residual (INIT: the stored initial residual)
     const double* d;
     double* ad;
     double* q;
     const double* scal;
     const int64_t* istat;
+    using Win = BandWin<B>;
+    static constexpr int W = Win::W, L = Win::L, H = Win::H;
     __device__ __forceinline__ bool skip() const { return ld_stat(istat + I_STATUS) != ST_RUNNING; }
-    // entry k of a vector / of the couplings, zero outside the matrix (clamped index + select: no divergent loads)
-    __device__ __forceinline__ double at(const double* v, int64_t k) const {
-        const int64_t kc = k < 0 ? 0 : (k >= A.n ? A.n - 1 : k);
-        const double x = v[kc];
-        return (k == kc) ? x : 0.0;
+    // entry r of a vector / of the couplings, zero outside the matrix (clamped index + select: no divergent loads)
+    __device__ __forceinline__ double at(const double* v, int64_t r) const {
+        const int64_t rc = r < 0 ? 0 : (r >= A.n ? A.n - 1 : r);
+        const double x = v[rc];
+        return (r == rc) ? x : 0.0;
     }
-    __device__ __forceinline__ double cpl(int64_t k) const {      // off_k couples rows k and k + 1: 0 <= k < n - 1
-        const int64_t kc = k < 0 ? 0 : (k >= A.n ? A.n - 1 : k);
-        const double x = A.off[kc];
-        return (k >= 0 && k + 1 < A.n) ? x : 0.0;
+    __device__ __forceinline__ double cpl(int k, int64_t r) const {      // off_k[r] couples rows r and r + k: 0 <= r < n - k
+        const int64_t rc = r < 0 ? 0 : (r >= A.n ? A.n - 1 : r);
+        const double x = A.col(k)[rc];
+        return (r >= 0 && r + k < A.n) ? x : 0.0;
     }
     __device__ __forceinline__ void apply(int64_t i, bool v0, bool v1, double*) const {
         if (!v0) return;
         const double alpha = INIT ? 0.0 : ld_scal(scal + S_ALPHA);
-        // rows i-1 .. i+2 of rr (and of A d): the two rows of this thread and one neighbour on either side
-        double o[5], adv[4], rr[4], gv[4], dv[6], axv[4];
-        if (i >= 2 && i + 4 < A.n) {                                             // interior (all but the first and the last thread): aligned pair loads
-            const double2 o0 = ld2(A.off + i - 2), o1 = ld2(A.off + i);
-            o[0] = o0.x; o[1] = o0.y; o[2] = o1.x; o[3] = o1.y; o[4] = A.off[i + 2];
-            const double2 g1 = ld2(g + i);
-            gv[0] = g[i - 1]; gv[1] = g1.x; gv[2] = g1.y; gv[3] = g[i + 2];
+        const int64_t r0 = i - 2 * B;                                            // row of window entry 0
+        double o[B][W], gv[W], dv[W], axv[W], rr[W], adv[W];
+        if (i >= 2 * B && i + 2 * B + 2 < A.n) {                                 // interior (all but the first and the last threads): aligned pair loads
+#pragma unroll
+            for (int k = 0; k < B; ++k) Win::pairs(A.col(k + 1), i, o[k]);
+            Win::pairs(g, i, gv);
             if (!INIT) {
-                const double2 d0 = ld2(d + i - 2), d1 = ld2(d + i), d2 = ld2(d + i + 2);
-                dv[0] = d0.x; dv[1] = d0.y; dv[2] = d1.x; dv[3] = d1.y; dv[4] = d2.x; dv[5] = d2.y;
+                Win::pairs(d, i, dv);
                 if (A.dg) {
-                    const double2 a1 = ld2(A.dg + i);
-                    axv[0] = A.a0 + A.dg[i - 1]; axv[1] = A.a0 + a1.x; axv[2] = A.a0 + a1.y; axv[3] = A.a0 + A.dg[i + 2];
+                    Win::pairs(A.dg, i, axv);
+#pragma unroll
+                    for (int t = L; t <= H; ++t) axv[t] += A.a0;
                 } else {
-                    axv[0] = axv[1] = axv[2] = axv[3] = A.a0;
+#pragma unroll
+                    for (int t = L; t <= H; ++t) axv[t] = A.a0;
                 }
             }
         } else {
 #pragma unroll
-            for (int k = 0; k < 5; ++k) o[k] = cpl(i - 2 + k);                   // off_{i-2} .. off_{i+2}
+            for (int k = 0; k < B; ++k)
 #pragma unroll
-            for (int k = 0; k < 4; ++k) gv[k] = at(g, i - 1 + k);
+                for (int t = L - k - 1; t <= H; ++t) o[k][t] = cpl(k + 1, r0 + t);
+#pragma unroll
+            for (int t = L; t <= H; ++t) gv[t] = at(g, r0 + t);
             if (!INIT) {
 #pragma unroll
-                for (int k = 0; k < 6; ++k) dv[k] = at(d, i - 2 + k);            // d_{i-2} .. d_{i+3}
+                for (int t = 0; t < W; ++t) dv[t] = at(d, r0 + t);
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int64_t r = i - 1 + k;
+                for (int t = L; t <= H; ++t) {
+                    const int64_t r = r0 + t;
                     const int64_t rc = r < 0 ? 0 : (r >= A.n ? A.n - 1 : r);
-                    axv[k] = A.a0 + (A.dg ? A.dg[rc] : 0.0);
+                    axv[t] = A.a0 + (A.dg ? A.dg[rc] : 0.0);
                 }
             }
         }
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {                                            // row i - 1 + k
-            adv[k] = INIT ? 0.0 : fma(o[k + 1], dv[k + 2], fma(o[k], dv[k], axv[k] * dv[k + 1]));   // same expression as TriMulF's for every row
-            rr[k] = INIT ? gv[k] : fma(alpha, adv[k], gv[k]);                    // :93
+        for (int t = L; t <= H; ++t) {                                           // row r0 + t: the same expression as TriMulF's for every row
+            double a = 0.0;
+            if (!INIT) {
+                a = axv[t] * dv[t];
+#pragma unroll
+                for (int k = 1; k <= B; ++k) a = fma(o[k - 1][t], dv[t + k], fma(o[k - 1][t - k], dv[t - k], a));
+            }
+            adv[t] = a;
+            rr[t] = INIT ? gv[t] : fma(alpha, a, gv[t]);                         // :93
         }
-        const double q0 = fma(o[2], rr[2], o[1] * rr[0]);
-        const double q1 = fma(o[3], rr[3], o[2] * rr[1]);
+        double qv[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int t = 2 * B + h;
+            double s = fma(o[0][t], rr[t + 1], o[0][t - 1] * rr[t - 1]);
+#pragma unroll
+            for (int k = 2; k <= B; ++k) s = fma(o[k - 1][t], rr[t + k], fma(o[k - 1][t - k], rr[t - k], s));
+            qv[h] = s;
+        }
         if (v1) {
-            st2(q + i, make_double2(q0, q1));
-            if (!INIT) st2(ad + i, make_double2(adv[1], adv[2]));
+            st2(q + i, make_double2(qv[0], qv[1]));
+            if (!INIT) st2(ad + i, make_double2(adv[2 * B], adv[2 * B + 1]));
         } else {
-            q[i] = q0;
-            if (!INIT) ad[i] = adv[1];
+            q[i] = qv[0];
+            if (!INIT) ad[i] = adv[2 * B];
         }
     }
 };
@@ -208,12 +253,13 @@ struct StackD {   // stacked (bound-constrained) basis Q = [[diag Dx; diag Dy], 
 };
 
 // TriPrepF for a stacked basis (PcgFuseTri<true, .>): A = blockdiag(T, diag(ay)) with T = diag(ax) + couplings on the x half (A.n = N rows, the y half
-// at A.dg + hs).  Per row k the pass projects rr = g + alpha A d onto the complement of the diagonal block, u_k = rr_k - D_k (D_k'rr_k) with
-// D_k = (Dx_k, Dy_k), and needs the neighbours' part of (T u)_x:  q_i = off_{i-1} ux_{i-1} + off_i ux_{i+1},  next to  ad_i = (T d)_i  (the x half of
-// A d; the y half ay dy is row-local).  INIT: rr is the stored initial residual, only q is written.  Nine streams of N doubles in, two out (88 N bytes).
-template <bool INIT>
+// at A.dg + hs).  Per row r the pass projects rr = g + alpha A d onto the complement of the diagonal block, u_r = rr_r - D_r (D_r'rr_r) with
+// D_r = (Dx_r, Dy_r), and needs the neighbours' part of (T u)_x:  q_i = sum_k (off_k[i-k] ux_{i-k} + off_k[i] ux_{i+k}),  next to  ad_i = (T d)_i
+// (the x half of A d; the y half ay dy is row-local).  INIT: rr is the stored initial residual, only q is written.  For B = 1 nine streams of N
+// doubles in, two out (88 N bytes); every further distance adds one coupling stream.
+template <int B, bool INIT>
 struct TriPrepSF {
-    TriD A;
+    BandD<B> A;
     int64_t hs;
     const double *Dx, *Dy;
     const double* g;          // stacked residual (INIT: the stored initial residual)
@@ -222,80 +268,92 @@ struct TriPrepSF {
     double* q;                // N
     const double* scal;
     const int64_t* istat;
+    using Win = BandWin<B>;
+    static constexpr int W = Win::W, L = Win::L, H = Win::H;
     __device__ __forceinline__ bool skip() const { return ld_stat(istat + I_STATUS) != ST_RUNNING; }
-    __device__ __forceinline__ double at(const double* v, int64_t k) const {      // (clamped index + select, as TriPrepF)
-        const int64_t kc = k < 0 ? 0 : (k >= A.n ? A.n - 1 : k);
-        const double x = v[kc];
-        return (k == kc) ? x : 0.0;
+    __device__ __forceinline__ double at(const double* v, int64_t r) const {      // (clamped index + select, as TriPrepF)
+        const int64_t rc = r < 0 ? 0 : (r >= A.n ? A.n - 1 : r);
+        const double x = v[rc];
+        return (r == rc) ? x : 0.0;
     }
-    __device__ __forceinline__ double cpl(int64_t k) const {
-        const int64_t kc = k < 0 ? 0 : (k >= A.n ? A.n - 1 : k);
-        const double x = A.off[kc];
-        return (k >= 0 && k + 1 < A.n) ? x : 0.0;
-    }
-    // rows i-1 .. i+2 of a vector (both halves share the row index): one pair load for the thread's own two rows
-    __device__ __forceinline__ void quad(const double* v, int64_t i, double (&o)[4]) const {
-        const double2 c = ld2(v + i);
-        o[0] = v[i - 1]; o[1] = c.x; o[2] = c.y; o[3] = v[i + 2];
+    __device__ __forceinline__ double cpl(int k, int64_t r) const {
+        const int64_t rc = r < 0 ? 0 : (r >= A.n ? A.n - 1 : r);
+        const double x = A.col(k)[rc];
+        return (r >= 0 && r + k < A.n) ? x : 0.0;
     }
     __device__ __forceinline__ void apply(int64_t i, bool v0, bool v1, double*) const {
         if (!v0) return;
         const double alpha = INIT ? 0.0 : ld_scal(scal + S_ALPHA);
-        double o[5], dxv[6], axv[4], gx[4], gy[4], dy[4], ay[4], Dxv[4], Dyv[4], adv[4], ux[4];
-        if (i >= 2 && i + 4 < A.n) {                                             // interior: aligned pair loads (hs is even)
-            const double2 o0 = ld2(A.off + i - 2), o1 = ld2(A.off + i);
-            o[0] = o0.x; o[1] = o0.y; o[2] = o1.x; o[3] = o1.y; o[4] = A.off[i + 2];
-            quad(g, i, gx); quad(g + hs, i, gy); quad(Dx, i, Dxv); quad(Dy, i, Dyv);
-            if (!INIT) {
-                const double2 d0 = ld2(d + i - 2), d1 = ld2(d + i), d2 = ld2(d + i + 2);
-                dxv[0] = d0.x; dxv[1] = d0.y; dxv[2] = d1.x; dxv[3] = d1.y; dxv[4] = d2.x; dxv[5] = d2.y;
-                quad(d + hs, i, dy);
-                if (A.dg) {
-                    quad(A.dg, i, axv); quad(A.dg + hs, i, ay);
+        const int64_t r0 = i - 2 * B;
+        double o[B][W], dxv[W], axv[W], gx[W], gy[W], dy[W], ay[W], Dxv[W], Dyv[W], adv[W], ux[W];
+        if (i >= 2 * B && i + 2 * B + 2 < A.n) {                                 // interior: aligned pair loads (hs is even)
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) { axv[k] += A.a0; ay[k] += A.a0; }
+            for (int k = 0; k < B; ++k) Win::pairs(A.col(k + 1), i, o[k]);
+            Win::pairs(g, i, gx); Win::pairs(g + hs, i, gy); Win::pairs(Dx, i, Dxv); Win::pairs(Dy, i, Dyv);
+            if (!INIT) {
+                Win::pairs(d, i, dxv);
+                Win::pairs(d + hs, i, dy);
+                if (A.dg) {
+                    Win::pairs(A.dg, i, axv); Win::pairs(A.dg + hs, i, ay);
+#pragma unroll
+                    for (int t = L; t <= H; ++t) { axv[t] += A.a0; ay[t] += A.a0; }
                 } else {
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) axv[k] = ay[k] = A.a0;
+                    for (int t = L; t <= H; ++t) axv[t] = ay[t] = A.a0;
                 }
             }
         } else {
 #pragma unroll
-            for (int k = 0; k < 5; ++k) o[k] = cpl(i - 2 + k);
+            for (int k = 0; k < B; ++k)
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int64_t r = i - 1 + k;
-                gx[k] = at(g, r); gy[k] = at(g + hs, r); Dxv[k] = at(Dx, r); Dyv[k] = at(Dy, r);
+                for (int t = L - k - 1; t <= H; ++t) o[k][t] = cpl(k + 1, r0 + t);
+#pragma unroll
+            for (int t = L; t <= H; ++t) {
+                const int64_t r = r0 + t;
+                gx[t] = at(g, r); gy[t] = at(g + hs, r); Dxv[t] = at(Dx, r); Dyv[t] = at(Dy, r);
             }
             if (!INIT) {
 #pragma unroll
-                for (int k = 0; k < 6; ++k) dxv[k] = at(d, i - 2 + k);
+                for (int t = 0; t < W; ++t) dxv[t] = at(d, r0 + t);
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int64_t r = i - 1 + k;
+                for (int t = L; t <= H; ++t) {
+                    const int64_t r = r0 + t;
                     const int64_t rc = r < 0 ? 0 : (r >= A.n ? A.n - 1 : r);
-                    dy[k] = at(d + hs, r);
-                    axv[k] = A.a0 + (A.dg ? A.dg[rc] : 0.0);
-                    ay[k] = A.a0 + (A.dg ? A.dg[hs + rc] : 0.0);
+                    dy[t] = at(d + hs, r);
+                    axv[t] = A.a0 + (A.dg ? A.dg[rc] : 0.0);
+                    ay[t] = A.a0 + (A.dg ? A.dg[hs + rc] : 0.0);
                 }
             }
         }
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {                                            // row i - 1 + k; the same expressions as PcgFuseTri<true, .>
-            adv[k] = INIT ? 0.0 : fma(o[k + 1], dxv[k + 2], fma(o[k], dxv[k], axv[k] * dxv[k + 1]));
-            const double rx = INIT ? gx[k] : fma(alpha, adv[k], gx[k]);          // :93
-            const double ry = INIT ? gy[k] : fma(alpha, ay[k] * dy[k], gy[k]);
-            const double ww = Dxv[k] * rx + Dyv[k] * ry;
-            ux[k] = rx - Dxv[k] * ww;
+        for (int t = L; t <= H; ++t) {                                           // row r0 + t; the same expressions as PcgFuseTri<true, .>
+            double a = 0.0;
+            if (!INIT) {
+                a = axv[t] * dxv[t];
+#pragma unroll
+                for (int k = 1; k <= B; ++k) a = fma(o[k - 1][t], dxv[t + k], fma(o[k - 1][t - k], dxv[t - k], a));
+            }
+            adv[t] = a;
+            const double rx = INIT ? gx[t] : fma(alpha, a, gx[t]);               // :93
+            const double ry = INIT ? gy[t] : fma(alpha, ay[t] * dy[t], gy[t]);
+            const double ww = Dxv[t] * rx + Dyv[t] * ry;
+            ux[t] = rx - Dxv[t] * ww;
         }
-        const double q0 = fma(o[2], ux[2], o[1] * ux[0]);
-        const double q1 = fma(o[3], ux[3], o[2] * ux[1]);
+        double qv[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int t = 2 * B + h;
+            double s = fma(o[0][t], ux[t + 1], o[0][t - 1] * ux[t - 1]);
+#pragma unroll
+            for (int k = 2; k <= B; ++k) s = fma(o[k - 1][t], ux[t + k], fma(o[k - 1][t - k], ux[t - k], s));
+            qv[h] = s;
+        }
         if (v1) {
-            st2(q + i, make_double2(q0, q1));
-            if (!INIT) st2(ad + i, make_double2(adv[1], adv[2]));
+            st2(q + i, make_double2(qv[0], qv[1]));
+            if (!INIT) st2(ad + i, make_double2(adv[2 * B], adv[2 * B + 1]));
         } else {
-            q[i] = q0;
-            if (!INIT) ad[i] = adv[1];
+            q[i] = qv[0];
+            if (!INIT) ad[i] = adv[2 * B];
         }
     }
 };
@@ -1197,44 +1255,58 @@ int lfpsqp_factored_basis_supported(const lfpsqp_ctx* ctx, const lfpsqp_mat* A, 
     return 0;
 }
 
-// ---- lfpsqp_projcg_tridiag: the reduced operator M = Z'A Z of a tridiagonal A, once per solve ----------------------------------------------------
-// With s_i = sign(off_i) and R_i = Z_i + s_i Z_{i+1} (rows of Z):  off_i (Z_i'Z_{i+1} + Z_{i+1}'Z_i) = |off_i| (R_i'R_i - Z_i'Z_i - Z_{i+1}'Z_{i+1}), so
-//     Z'A Z = R' diag(|off|) R + Z' diag(c) Z,    c_i = a0 + dg_i - |off_i| - |off_{i-1}|,
-// i.e. weighted Gram matrices on the matrix cores -- the kernel of the tangent set-up, which forms the rows of R in registers on their way to
-// LDS (gram_kernel SHIFT): two passes over Z, no scratch matrix.  The first term is a sum of squares whatever the signs of the couplings (for a
-// discrete Laplacian, off = -1, it is the whole of M: no cancellation); c is non-negative for a diagonally dominant A, otherwise its negative
-// part costs a third pass.
-__global__ __launch_bounds__(256) void tri_weights_kernel(TriD A, double* __restrict__ wabs, double* __restrict__ sgn, double* __restrict__ cpos, double* __restrict__ cneg,
+// ---- lfpsqp_projcg_tridiag / lfpsqp_projcg_band: the reduced operator M = Z'A Z of a banded A, once per solve ---------------------------------
+// With s_k[i] = sign(off_k[i]) and R_{k,i} = Z_i + s_k[i] Z_{i+k} (rows of Z):
+//     off_k[i] (Z_i'Z_{i+k} + Z_{i+k}'Z_i) = |off_k[i]| (R_{k,i}'R_{k,i} - Z_i'Z_i - Z_{i+k}'Z_{i+k}),  so
+//     Z'A Z = sum_{k=1..B} R_k' diag(|off_k|) R_k + Z' diag(c) Z,    c_i = a0 + dg_i - sum_k (|off_k[i]| + |off_k[i-k]|),
+// i.e. weighted Gram matrices on the matrix cores -- the kernel of the tangent set-up, which forms the rows of R_k in registers on their way to
+// LDS (gram_kernel SHIFT = k): B + 1 passes over Z, no scratch matrix.  The first terms are sums of squares whatever the signs of the couplings
+// (for a discrete Laplacian, off = -1, they are the whole of M: no cancellation); c is non-negative for a diagonally dominant A, otherwise its
+// negative part costs one more pass (the normal case for second differences, interior stencil kappa [1, -4, 6, -4, 1]).  The passes are summed
+// in the order k = 1 .. B, + cpos, - cneg.
+template <int B>
+__global__ __launch_bounds__(256) void tri_weights_kernel(BandD<B> A, double* __restrict__ wabs /* B columns, npad apart */,
+                                                          double* __restrict__ sgn /* B columns */, double* __restrict__ cpos, double* __restrict__ cneg,
                                                           int64_t npad, double* __restrict__ anyneg) {
     bool neg = false;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < npad; i += (int64_t)gridDim.x * 256) {
-        double wa = 0.0, sg = 1.0, cp = 0.0, cn = 0.0;
+        double cp = 0.0, cn = 0.0;
+        double c = (i < A.n) ? A.a0 + (A.dg ? A.dg[i] : 0.0) : 0.0;
+#pragma unroll
+        for (int k = 1; k <= B; ++k) {
+            double wa = 0.0, sg = 1.0;
+            if (i < A.n) {
+                const double o = (i + k < A.n) ? A.col(k)[i] : 0.0;
+                wa = fabs(o);
+                sg = (o < 0.0) ? -1.0 : 1.0;
+                const double wm = (i >= k) ? fabs(A.col(k)[i - k]) : 0.0;
+                c = c - wa - wm;
+            }
+            wabs[(k - 1) * npad + i] = wa; sgn[(k - 1) * npad + i] = sg;
+        }
         if (i < A.n) {
-            const double o = (i + 1 < A.n) ? A.off[i] : 0.0;
-            wa = fabs(o);
-            sg = (o < 0.0) ? -1.0 : 1.0;
-            const double wm = (i > 0) ? fabs(A.off[i - 1]) : 0.0;
-            const double c = A.a0 + (A.dg ? A.dg[i] : 0.0) - wa - wm;
             if (c >= 0.0) cp = c;
             else { cn = -c; neg = true; }
             if (c != c) cp = c;                               // (NaN data: let the Gram pass report it)
         }
-        wabs[i] = wa; sgn[i] = sg; cpos[i] = cp; cneg[i] = cn;
+        cpos[i] = cp; cneg[i] = cn;
     }
     if (neg) *anyneg = 1.0;
 }
-// stacked basis: the reduced operator Q_Z'A Q_Z = Z' At Z of the tridiagonal At = S_x T S_x + S_y diag(ay) S_y (PcgFuseTri<true, .>) -- the same Gram
-// passes as above, over At instead of A
-__global__ __launch_bounds__(256) void tri_stack_weights_kernel(TriD A, int64_t hs, const double* __restrict__ sx, const double* __restrict__ sy,
-                                                                double* __restrict__ adg, double* __restrict__ aoff, int64_t npad) {
+// stacked basis: the reduced operator Q_Z'A Q_Z = Z' At Z of the banded At = S_x T S_x + S_y diag(ay) S_y (PcgFuseTri<true, .>) -- the same Gram
+// passes as above, over At instead of A:  At_ii = sx_i^2 ax_i + sy_i^2 ay_i,  At_{i,i+k} = sx_i off_k[i] sx_{i+k}
+template <int B>
+__global__ __launch_bounds__(256) void tri_stack_weights_kernel(BandD<B> A, int64_t hs, const double* __restrict__ sx, const double* __restrict__ sy,
+                                                                double* __restrict__ adg, double* __restrict__ aoff /* B columns, npad apart */, int64_t npad) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < npad; i += (int64_t)gridDim.x * 256) {
-        double dv = 0.0, ov = 0.0;
+        double dv = 0.0;
         if (i < A.n) {
             const double ax = A.a0 + (A.dg ? A.dg[i] : 0.0), ay = A.a0 + (A.dg ? A.dg[hs + i] : 0.0);
             dv = fma(sx[i] * sx[i], ax, sy[i] * sy[i] * ay);
-            if (i + 1 < A.n) ov = sx[i] * A.off[i] * sx[i + 1];
         }
-        adg[i] = dv; aoff[i] = ov;
+        adg[i] = dv;
+#pragma unroll
+        for (int k = 1; k <= B; ++k) aoff[(k - 1) * npad + i] = (i + k < A.n) ? sx[i] * A.col(k)[i] * sx[i + k] : 0.0;
     }
 }
 static int ensure_tri(lfpsqp_ctx* ctx, size_t doubles) {
@@ -1249,33 +1321,39 @@ static int ensure_tri(lfpsqp_ctx* ctx, size_t doubles) {
 }
 // Mh (m x m, column-major, host) = U'A U for U = Z[:, :mc] (W == nullptr, m == mc) or U = Z[:, :mc] W (W: mc x m, host); sk: a stacked basis,
 // U = [sx; sy] .* (that), and A over the x half (A.n = N rows, dg stacked)
-static int tri_reduced_operator(lfpsqp_ctx* ctx, const lfpsqp_mat* Z, int mc, const TriD& A0, const double* W, int m, std::vector<double>& Mh,
+template <int B>
+static int tri_reduced_operator(lfpsqp_ctx* ctx, const lfpsqp_mat* Z, int mc, const BandD<B>& A0, const double* W, int m, std::vector<double>& Mh,
                                 const StackD* sk = nullptr) {
     const int64_t n = A0.n, npad = round_up((n > 0 ? n : 1) + 1, kPadRows);
-    LF_TRY(ensure_tri(ctx, (sk ? 6 : 4) * (size_t)npad + 8));
+    LF_TRY(ensure_tri(ctx, (2 * B + 2 + (sk ? 1 + B : 0)) * (size_t)npad + 8));
     double* wabs = ctx->d_tri;
-    double* sgn = wabs + npad;
-    double* cpos = sgn + npad;
+    double* sgn = wabs + B * npad;
+    double* cpos = sgn + B * npad;
     double* cneg = cpos + npad;
     double* anyneg = cneg + npad;
-    TriD A = A0;
+    BandD<B> A = A0;
+    const unsigned nblk = (unsigned)std::min<int64_t>((npad + 255) / 256, 4096);
     if (sk) {
         double* adg = anyneg + 8;
         double* aoff = adg + npad;
-        hipLaunchKernelGGL(tri_stack_weights_kernel, dim3((int)std::min<int64_t>((npad + 255) / 256, 4096)), dim3(256), 0, ctx->stream, A0, sk->hs, sk->sx,
-                           sk->sy, adg, aoff, npad);
+        hipLaunchKernelGGL(tri_stack_weights_kernel<B>, dim3(nblk), dim3(256), 0, ctx->stream, A0, sk->hs, sk->sx, sk->sy, adg, aoff, npad);
         LF_LAUNCH_CHECK(ctx);
-        A = TriD{0.0, adg, aoff, n, n};
+        A = BandD<B>{0.0, adg, aoff, npad, n, n};
     }
     LF_HIP(ctx, hipMemsetAsync(anyneg, 0, sizeof(double), ctx->stream));
-    hipLaunchKernelGGL(tri_weights_kernel, dim3((int)std::min<int64_t>((npad + 255) / 256, 4096)), dim3(256), 0, ctx->stream, A, wabs, sgn, cpos, cneg, npad, anyneg);
+    hipLaunchKernelGGL(tri_weights_kernel<B>, dim3(nblk), dim3(256), 0, ctx->stream, A, wabs, sgn, cpos, cneg, npad, anyneg);
     LF_LAUNCH_CHECK(ctx);
     double hneg = 0.0;
     LF_HIP(ctx, hipMemcpyAsync(&hneg, anyneg, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const lfpsqp_mat Zp = Z->plain();
     std::vector<double> G, G2((size_t)mc * mc);
-    LF_TRY(gram_shifted(ctx, &Zp, mc, wabs, sgn, G));
+    LF_TRY(gram_shifted(ctx, &Zp, mc, wabs, sgn, G, 1));
+    for (int k = 2; k <= B; ++k) {
+        LF_TRY(gram_shifted(ctx, &Zp, mc, wabs + (k - 1) * npad, sgn + (k - 1) * npad, G2, k));
+        for (size_t e = 0; e < G.size(); ++e) G[e] += G2[e];
+    }
+    G2.resize((size_t)mc * mc);
     lfpsqp_vec wv;
     wv.n = n; wv.cap = npad;
     wv.p = cpos;
@@ -1305,10 +1383,30 @@ static int tri_reduced_operator(lfpsqp_ctx* ctx, const lfpsqp_mat* Z, int mc, co
     return 0;
 }
 
+// the banded operator of lfpsqp_projcg_tridiag (bw = 1, off a vector) and lfpsqp_projcg_band (off a plain matrix): bw coupling columns of `rows`
+// entries, ld apart
+struct BandOp {
+    double a0;
+    const lfpsqp_vec* dg;
+    const double* off;
+    int64_t ld, rows;
+    int bw;
+};
+// fn(std::integral_constant<int, B>) for B = bw (1 .. 4)
+template <typename F>
+static int with_band(int bw, F&& fn) {
+    switch (bw) {
+        case 1: return fn(std::integral_constant<int, 1>{});
+        case 2: return fn(std::integral_constant<int, 2>{});
+        case 3: return fn(std::integral_constant<int, 3>{});
+        default: return fn(std::integral_constant<int, 4>{});
+    }
+}
+
 static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const lfpsqp_diag_op* A, lfpsqp_opfun opf, void* ouser,
                        lfpsqp_vec* Av, const lfpsqp_basis* U, const lfpsqp_vec* b, const lfpsqp_vec* c, double tol, int64_t maxit,
                        int64_t n_global, int flags, const lfpsqp_projcg_work* work, int64_t* iters, double* nr,
-                       const lfpsqp_lowrank_op* LRop = nullptr, const lfpsqp_tridiag_op* TRop = nullptr) {
+                       const lfpsqp_lowrank_op* LRop = nullptr, const BandOp* TRop = nullptr) {
     const lfpsqp_diag_op no_diag = {0.0, nullptr};
     lfpsqp_diag_op lr_diag = {0.0, nullptr};
     if (LRop) { lr_diag.a0 = LRop->a0; lr_diag.dg = LRop->dg; A = &lr_diag; }
@@ -1410,19 +1508,23 @@ static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const
         if (!fused || stacked || (flags & (LFPSQP_PROJCG_RESUME | LFPSQP_PROJCG_START_GIVEN | LFPSQP_PROJCG_START_PROJECTED)))
             return set_err(ctx, LFPSQP_ERR_UNSUPPORTED, "lfpsqp_projcg_lowrank: needs the one-pass iteration over a plain dense basis (4 .. 1024 columns), no RESUME / START_GIVEN");
     }
-    // tridiagonal operator (lfpsqp_projcg_tridiag): fused iteration only; M = U'A U first (its Gram passes use the scratch areas reserved below)
+    // tridiagonal / banded operator (lfpsqp_projcg_tridiag, lfpsqp_projcg_band): fused iteration only; M = U'A U first (its Gram passes use the
+    // scratch areas reserved below).  Over the x half: BandD<B>{a0, dg, off, ld, N, N}; over whole (stacked) vectors (lfpsqp_tridiag_mul's form):
+    // n = nv, nc = N.
     std::vector<double> triMh;
-    TriD Atri{0.0, nullptr, nullptr, 0, 0};
-    TriD AtriMul = Atri;                               // the operator over whole (stacked) vectors: lfpsqp_tridiag_mul's form
+    const double* tri_dg = (TRop && TRop->dg) ? TRop->dg->p : nullptr;
     if (TRop) {
-        // (stacked: dg over both halves, off the x half's couplings -- length N; the y half is diagonal)
-        LF_ARG(ctx, TRop->off && TRop->off->n == N && (!TRop->dg || TRop->dg->n == nv));
+        // (stacked: dg over both halves, off the x half's couplings -- N rows; the y half is diagonal)
+        LF_ARG(ctx, TRop->off && TRop->rows == N && TRop->bw >= 1 && TRop->bw <= 4 && (!TRop->dg || TRop->dg->n == nv));
         if (!fused || !plain_mat(Z) || ctx->comm_active())
-            return set_err(ctx, LFPSQP_ERR_UNSUPPORTED, "lfpsqp_projcg_tridiag: needs the one-pass iteration over a dense basis (4 .. 1024 columns, no matrix "
-                                                        "view) on a single rank (the couplings would cross the shard boundaries); use lfpsqp_projcg_op");
-        Atri = TriD{TRop->a0, TRop->dg ? TRop->dg->p : nullptr, TRop->off->p, N, N};
-        AtriMul = TriD{Atri.a0, Atri.dg, Atri.off, nv, N};
-        LF_TRY(tri_reduced_operator(ctx, Z, mc, Atri, DF ? U->W : nullptr, m, triMh, stacked ? &sk : nullptr));
+            return set_err(ctx, LFPSQP_ERR_UNSUPPORTED, "%s: needs the one-pass iteration over a dense basis (4 .. 1024 columns, no matrix "
+                                                        "view) on a single rank (the couplings would cross the shard boundaries); use lfpsqp_projcg_op",
+                           TRop->bw == 1 ? "lfpsqp_projcg_tridiag" : "lfpsqp_projcg_band");
+        LF_TRY(with_band(TRop->bw, [&](auto Bc) -> int {
+            constexpr int B = decltype(Bc)::value;
+            return tri_reduced_operator<B>(ctx, Z, mc, BandD<B>{TRop->a0, tri_dg, TRop->off, TRop->ld, N, N}, DF ? U->W : nullptr, m, triMh,
+                                           stacked ? &sk : nullptr);
+        }));
     }
     double* dTriM = nullptr;
     double *lrUtV = nullptr, *lrSig = nullptr, *lrVdraw = nullptr, *lrVdc = nullptr, *lrVtv = nullptr;
@@ -1486,7 +1588,11 @@ static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const
             return residual_with(AOpLR{Ad.a0, Ad.dg, LRop->V->p, LRop->V->ld, kLR, lrSig, lrVtv}, sgn, store, t_out);
         }
         if (TRop) {                                                           // Av = A x by the stencil kernel, then as a stored product
-            LF_TRY((run_vec<TriMulF, 0, NoPost>(ctx, nv, TriMulF{AtriMul, x->p, Av->p, nullptr}, 0u, nullptr, NoPost())));
+            LF_TRY(with_band(TRop->bw, [&](auto Bc) -> int {
+                constexpr int B = decltype(Bc)::value;
+                const BandD<B> Am{TRop->a0, tri_dg, TRop->off, TRop->ld, nv, N};
+                return run_vec<TriMulF<B>, 0, NoPost>(ctx, nv, TriMulF<B>{Am, x->p, Av->p, nullptr}, 0u, nullptr, NoPost());
+            }));
             return residual_with(Aop, sgn, store, t_out);
         }
         if (!opf) return residual_with(Ad, sgn, store, t_out);
@@ -1537,20 +1643,27 @@ static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const
         double* gout = init ? gbuf[0] : gbuf[gcur ^ 1];
         const double* tin = DF ? uDF : Utr;               // coefficients of the first product over the streamed matrix's mc columns
         double* Tout = DF ? Traw : T12;
-        // tridiagonal: the neighbours' contributions first (a vector kernel), into Av while rp still holds the initial residual, into rp afterwards
-        // (stacked: both into the first N entries)
-        if (TRop && stacked && init) {
-            LF_TRY((run_vec<TriPrepSF<true>, 0, NoPost>(ctx, N, TriPrepSF<true>{Atri, hs, sk.Dx, sk.Dy, rp, nullptr, nullptr, Av->p, scal, istat}, 0u, nullptr, NoPost())));
-            LF_TRY((run_onepass<PcgFuseTri<true, true>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseTri<true, true>{rp, gin, gout, d, nullptr, Av->p, Ad, scal, istat, sk}, Tout, slot)));
-        } else if (TRop && stacked) {
-            LF_TRY((run_vec<TriPrepSF<false>, 0, NoPost>(ctx, N, TriPrepSF<false>{Atri, hs, sk.Dx, sk.Dy, gin, d, Av->p, rp, scal, istat}, 0u, nullptr, NoPost())));
-            LF_TRY((run_onepass<PcgFuseTri<true, false>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseTri<true, false>{rp, gin, gout, d, Av->p, rp, Ad, scal, istat, sk}, Tout, slot)));
-        } else if (TRop && init) {
-            LF_TRY((run_vec<TriPrepF<true>, 0, NoPost>(ctx, nv, TriPrepF<true>{Atri, rp, nullptr, nullptr, Av->p, scal, istat}, 0u, nullptr, NoPost())));
-            LF_TRY((run_onepass<PcgFuseTri<false, true>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseTri<false, true>{rp, gin, gout, d, nullptr, Av->p, Ad, scal, istat, sk}, Tout, slot)));
-        } else if (TRop) {
-            LF_TRY((run_vec<TriPrepF<false>, 0, NoPost>(ctx, nv, TriPrepF<false>{Atri, gin, d, Av->p, rp, scal, istat}, 0u, nullptr, NoPost())));
-            LF_TRY((run_onepass<PcgFuseTri<false, false>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseTri<false, false>{rp, gin, gout, d, Av->p, rp, Ad, scal, istat, sk}, Tout, slot)));
+        // tridiagonal / banded: the neighbours' contributions first (a vector kernel), into Av while rp still holds the initial residual, into rp
+        // afterwards (stacked: both into the first N entries).  The pass itself does not depend on the bandwidth.
+        if (TRop) {
+            LF_TRY(with_band(TRop->bw, [&](auto Bc) -> int {
+                constexpr int B = decltype(Bc)::value;
+                const BandD<B> Ab{TRop->a0, tri_dg, TRop->off, TRop->ld, N, N};
+                if (stacked && init) {
+                    LF_TRY((run_vec<TriPrepSF<B, true>, 0, NoPost>(ctx, N, TriPrepSF<B, true>{Ab, hs, sk.Dx, sk.Dy, rp, nullptr, nullptr, Av->p, scal, istat}, 0u, nullptr, NoPost())));
+                    LF_TRY((run_onepass<PcgFuseTri<true, true>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseTri<true, true>{rp, gin, gout, d, nullptr, Av->p, Ad, scal, istat, sk}, Tout, slot)));
+                } else if (stacked) {
+                    LF_TRY((run_vec<TriPrepSF<B, false>, 0, NoPost>(ctx, N, TriPrepSF<B, false>{Ab, hs, sk.Dx, sk.Dy, gin, d, Av->p, rp, scal, istat}, 0u, nullptr, NoPost())));
+                    LF_TRY((run_onepass<PcgFuseTri<true, false>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseTri<true, false>{rp, gin, gout, d, Av->p, rp, Ad, scal, istat, sk}, Tout, slot)));
+                } else if (init) {
+                    LF_TRY((run_vec<TriPrepF<B, true>, 0, NoPost>(ctx, nv, TriPrepF<B, true>{Ab, rp, nullptr, nullptr, Av->p, scal, istat}, 0u, nullptr, NoPost())));
+                    LF_TRY((run_onepass<PcgFuseTri<false, true>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseTri<false, true>{rp, gin, gout, d, nullptr, Av->p, Ad, scal, istat, sk}, Tout, slot)));
+                } else {
+                    LF_TRY((run_vec<TriPrepF<B, false>, 0, NoPost>(ctx, nv, TriPrepF<B, false>{Ab, gin, d, Av->p, rp, scal, istat}, 0u, nullptr, NoPost())));
+                    LF_TRY((run_onepass<PcgFuseTri<false, false>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseTri<false, false>{rp, gin, gout, d, Av->p, rp, Ad, scal, istat, sk}, Tout, slot)));
+                }
+                return 0;
+            }));
         }
         else if (kLR > 0 && init) LF_TRY((run_onepass<PcgFuseLR<true>, 2, 5 + kLRMax>(ctx, Z, mc, mc, N, tin, PcgFuseLR<true>{rp, gin, gout, d, Ad, scal, istat, LRop->V->p, LRop->V->ld, kLR, lrVdc}, Tout, slot)));
         else if (kLR > 0) LF_TRY((run_onepass<PcgFuseLR<false>, 2, 5 + kLRMax>(ctx, Z, mc, mc, N, tin, PcgFuseLR<false>{rp, gin, gout, d, Ad, scal, istat, LRop->V->p, LRop->V->ld, kLR, lrVdc}, Tout, slot)));
@@ -1757,18 +1870,43 @@ extern "C" int lfpsqp_projcg_tridiag(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec*
                                      const lfpsqp_vec* b, const lfpsqp_vec* c, double tol, int64_t maxit, int64_t n_global, int flags,
                                      const lfpsqp_projcg_work* work, int64_t* iters, double* nr) {
     LF_RANGE("lfpsqp_projcg_tridiag");
-    LF_ARG(ctx, ctx && A && Av);
-    return projcg_impl(ctx, x, lambda, nullptr, nullptr, nullptr, Av, U, b, c, tol, maxit, n_global, flags, work, iters, nr, nullptr, A);
+    LF_ARG(ctx, ctx && A && Av && A->off);
+    const BandOp bop{A->a0, A->dg, A->off->p, A->off->n, A->off->n, 1};
+    return projcg_impl(ctx, x, lambda, nullptr, nullptr, nullptr, Av, U, b, c, tol, maxit, n_global, flags, work, iters, nr, nullptr, &bop);
+}
+
+extern "C" int lfpsqp_projcg_band(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, double a0, const lfpsqp_vec* dg, const lfpsqp_mat* off, int64_t bw,
+                                  lfpsqp_vec* Av, const lfpsqp_basis* U, const lfpsqp_vec* b, const lfpsqp_vec* c, double tol, int64_t maxit,
+                                  int64_t n_global, int flags, const lfpsqp_projcg_work* work, int64_t* iters, double* nr) {
+    LF_RANGE("lfpsqp_projcg_band");
+    LF_ARG(ctx, ctx && Av && off && plain_mat(off) && bw >= 1 && bw <= 4 && off->m >= bw);
+    const BandOp bop{a0, dg, off->p, off->ld, off->n, (int)bw};
+    return projcg_impl(ctx, x, lambda, nullptr, nullptr, nullptr, Av, U, b, c, tol, maxit, n_global, flags, work, iters, nr, nullptr, &bop);
+}
+
+// out = A v for the banded operator: off of n rows, or of N rows for a stacked pair (v->n = half stride + N: the couplings act on the x half,
+// the rest is diagonal)
+static int band_mul(lfpsqp_ctx* ctx, const char* who, double a0, const lfpsqp_vec* dg, const double* off, int64_t ld, int64_t rows, int bw,
+                    const lfpsqp_vec* v, lfpsqp_vec* out) {
+    LF_ARG(ctx, v && out && v != out && v->p != out->p && out->n == v->n && (!dg || dg->n == v->n));
+    LF_ARG(ctx, rows == v->n || (rows > 0 && v->n == lfpsqp_half_stride(rows) + rows));
+    if (ctx->comm_active())        // (a rank sees its own rows only: the couplings across the shard boundaries would silently drop out)
+        return set_err(ctx, LFPSQP_ERR_UNSUPPORTED, "%s: one rank only (no halo exchange between row shards)", who);
+    return with_band(bw, [&](auto Bc) -> int {
+        constexpr int B = decltype(Bc)::value;
+        const BandD<B> A{a0, dg ? dg->p : nullptr, off, ld, v->n, rows};
+        return run_vec<TriMulF<B>, 0, NoPost>(ctx, v->n, TriMulF<B>{A, v->p, out->p, nullptr}, 0u, nullptr, NoPost());
+    });
 }
 
 extern "C" int lfpsqp_tridiag_mul(lfpsqp_ctx* ctx, const lfpsqp_tridiag_op* A, const lfpsqp_vec* v, lfpsqp_vec* out) {
-    // off of length n, or of length N for a stacked pair (v->n = half stride + N: the couplings act on the x half, the rest is diagonal)
-    LF_ARG(ctx, ctx && A && A->off && v && out && v != out && v->p != out->p && out->n == v->n && (!A->dg || A->dg->n == v->n));
-    LF_ARG(ctx, A->off->n == v->n || (A->off->n > 0 && v->n == lfpsqp_half_stride(A->off->n) + A->off->n));
-    if (ctx->comm_active())        // (a rank sees its own rows only: the couplings across the shard boundaries would silently drop out)
-        return set_err(ctx, LFPSQP_ERR_UNSUPPORTED, "lfpsqp_tridiag_mul: one rank only (no halo exchange between row shards)");
-    return run_vec<TriMulF, 0, NoPost>(ctx, v->n, TriMulF{TriD{A->a0, A->dg ? A->dg->p : nullptr, A->off->p, v->n, A->off->n}, v->p, out->p, nullptr}, 0u, nullptr,
-                                       NoPost());
+    LF_ARG(ctx, ctx && A && A->off);
+    return band_mul(ctx, "lfpsqp_tridiag_mul", A->a0, A->dg, A->off->p, A->off->n, A->off->n, 1, v, out);
+}
+
+extern "C" int lfpsqp_band_mul(lfpsqp_ctx* ctx, double a0, const lfpsqp_vec* dg, const lfpsqp_mat* off, int64_t bw, const lfpsqp_vec* v, lfpsqp_vec* out) {
+    LF_ARG(ctx, ctx && off && plain_mat(off) && bw >= 1 && bw <= 4 && off->m >= bw);
+    return band_mul(ctx, "lfpsqp_band_mul", a0, dg, off->p, off->ld, off->n, (int)bw, v, out);
 }
 
 extern "C" int lfpsqp_projcg_op(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, lfpsqp_opfun A, void* user, lfpsqp_vec* Av,

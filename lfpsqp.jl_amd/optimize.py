@@ -183,8 +183,9 @@ def optimize_core(f, grad_, c_, jac_, hess_lag_vec_, x0, xl, xu, m: int, param: 
     # The LIBRARY says whether this context can run projcg without Z for this Jct (one-pass kernels on, shape and leading dimension inside
     # their limits, or a sparse twin the nonzero path covers); where it cannot (LFPSQP_ONEPASS=-1, ld beyond the 32-bit lane offsets ...)
     # Z is materialised and every path has its two-pass form.
-    # (a tridiagonal Hessian sent through the callback path -- DeviceOptions.tridiagonal_one_pass off -- needs the materialised basis)
-    tri_callback = diagonal_hessian and getattr(hess_lag_vec_, "offdiag", None) is not None and not bool(getattr(ctx.options, "tridiagonal_one_pass", True))
+    # (a tridiagonal or banded Hessian sent through the callback path -- DeviceOptions.tridiagonal_one_pass off -- needs the materialised basis)
+    coupled_hessian = diagonal_hessian and (getattr(hess_lag_vec_, "offdiag", None) is not None or getattr(hess_lag_vec_, "offdiags", None) is not None)
+    tri_callback = coupled_hessian and not bool(getattr(ctx.options, "tridiagonal_one_pass", True))
     factored = (bool(ctx.options.factored_basis) and diagonal_hessian and not tri_callback and 4 <= m <= 1024
                 and ctx.factored_basis_supported(Jct, getattr(c_, "Jsp", None)))
     # Allocation by trial costs tens of milliseconds (18 timed launches of F at n = 1e7, m = 128: 36 ms) and returns 3 % of every projected-CG
@@ -216,8 +217,11 @@ def optimize_core(f, grad_, c_, jac_, hess_lag_vec_, x0, xl, xu, m: int, param: 
     # couplings -- projcg_ keeps one pass per iteration with it (lfpsqp_projcg_tridiag; one rank: the operator's own limit).  With bounds the
     # Newton map is blockdiag(H + 2 lamy.*q, 2 lamy.*s) (src/inequality_helper.jl:144-158): the augmented diagonal (stacked, lfpsqp_augmented_diag
     # or the tangent step, as for a diagonal Hessian) next to the same couplings on the x half
+    # A BANDED one (bandwidth 2 .. 4: second or higher differences) exposes ``offdiags`` instead, an N x bw device matrix whose column k-1 couples
+    # variables i and i+k: the same rules, lfpsqp_projcg_band
     tri_off = getattr(hess_lag_vec_, "offdiag", None) if diagonal_hessian else None
-    if tri_off is not None:
+    band_off = getattr(hess_lag_vec_, "offdiags", None) if (diagonal_hessian and tri_off is None) else None
+    if tri_off is not None or band_off is not None:
         # (the tangent step's pass still hands projcg_ r0 and U'r0 -- neither involves A --, but never its folded initial projection, whose
         # sums are formed with the diagonal alone: init_fold stays off below)
         if not bool(getattr(ctx.options, "tridiagonal_one_pass", True)):
@@ -231,6 +235,11 @@ def optimize_core(f, grad_, c_, jac_, hess_lag_vec_, x0, xl, xu, m: int, param: 
         from .projcg import TridiagonalOperator
         a_diag = projcgwork.placed_extra[0] if projcgwork.placed_extra else newvec()
         newton_map = TridiagonalOperator(0.0, a_diag, tri_off)
+        newton_map.fused = bool(getattr(ctx.options, "tridiagonal_one_pass", True))
+    elif band_off is not None:
+        from .projcg import BandedOperator
+        a_diag = projcgwork.placed_extra[0] if projcgwork.placed_extra else newvec()
+        newton_map = BandedOperator(0.0, a_diag, band_off, band_off.m)
         newton_map.fused = bool(getattr(ctx.options, "tridiagonal_one_pass", True))
     elif diagonal_hessian:
         a_diag = projcgwork.placed_extra[0] if projcgwork.placed_extra else newvec()
@@ -332,7 +341,7 @@ def optimize_core(f, grad_, c_, jac_, hess_lag_vec_, x0, xl, xu, m: int, param: 
                 # (flag 1 = LFPSQP_TANGENT_INIT_PROJCG: the pass is projcg!'s initial projection as well -- src/projcg.jl:58-62 -- with U'r0 from
                 # the Gram matrix; projcg_ then starts with its first iteration, start_projected=True.  Only where the Gram matrix resolves
                 # I - U'U: a full-rank block with cond^2 <= 10, the fast path of the factorisation; otherwise projcg_ measures U'r0 itself)
-                init_fold = bool(tri_off is None and rank == m and S_[0] * S_[0] <= 10.0 * S_[m - 1] * S_[m - 1])
+                init_fold = bool(tri_off is None and band_off is None and rank == m and S_[0] * S_[0] <= 10.0 * S_[m - 1] * S_[m - 1])
                 ctx.check(ctx.L.lfpsqp_tangent_step(ctx.h, C.byref(bs), sig_c.ctypes.data, vt_c.ctypes.data, m, Jtd.ctypes.data, Ggram.ctypes.data, d.h,
                                                     C.byref(cc) if cc is not None else None, x.h, a_diag.h,
                                                     C.byref(idc) if ineq else None, hx.h if ineq else None, idecomp.S.h if ineq else None,

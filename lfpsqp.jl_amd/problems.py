@@ -164,42 +164,72 @@ class SeparableLinearBallBox(QuadLinearBallBox):
         return np.concatenate([x0, [out.value - self.R2]]), np.concatenate([xl, [-np.inf]]), np.concatenate([xu, [0.0]])
 
 
-class ChainSeparableLinear(SeparableLinearBallBox):
-    """A separable objective plus a CHAIN term: f(x) = sum_i phi(x_i - c_i; a_i) + kappa/2 sum_{i<n-1} (x_{i+1} - x_i)^2 (smoothing / first
-    differences -- the kind of objective whose Hessian the reference reaches only through hess_lag_vec!, src/autodiff_generators.jl:72-107)
-    under dense linear equalities, with the optional ball (slack variable) and box bounds of :class:`QuadLinearBallBox`.  The Lagrangian Hessian
-    is TRIDIAGONAL: diagonal phi''(x_i) + kappa deg_i (+ 2 lam_ball; deg = 1 at the two ends, 2 inside), couplings -kappa; the slack row, when
-    the ball is there, has neither.  ``optimize`` hands it to projcg_ as a :class:`TridiagonalOperator` (``offdiag`` below; with bounds the
-    augmented stacked diagonal next to the same couplings): the truncated-Newton solves keep one pass over the basis per iteration
-    (lfpsqp_projcg_tridiag).  One rank (the couplings would cross the shard boundaries)."""
+def difference_band(n: int, order: int, kappa: float = 1.0):
+    """The diagonal (length n) and the ``order`` off-diagonals (n x order, column k-1: entry i couples i and i+k; the last k entries zero) of
+    kappa D'D, D the (n - order) x n matrix of ``order``-th forward differences (boundary rows included)."""
+    from math import comb
+    cf = np.array([(-1.0) ** (order - t) * comb(order, t) for t in range(order + 1)])       # row j of D: cf[t] at column j + t
+    rows = max(n - order, 0)
+    diag = np.zeros(n)
+    off = np.zeros((n, order))
+    for t in range(order + 1):
+        diag[t:t + rows] += cf[t] * cf[t]
+        for k in range(1, order + 1 - t):
+            off[t:t + rows, k - 1] += cf[t] * cf[t + k]
+    return kappa * diag, kappa * off
 
-    def __init__(self, ctx: Context, n: int, m: int, Jct: DeviceMatrix, b, kind: int, a, c=0.0, kappa: float = 1.0, **kw):
+
+class ChainSeparableLinear(SeparableLinearBallBox):
+    """A separable objective plus a CHAIN term: f(x) = sum_i phi(x_i - c_i; a_i) + kappa/2 ||D^r x||^2, D^r the r-th forward difference over the n
+    user variables (``order`` r = 1 .. 4; r = 1: kappa/2 sum_{i<n-1} (x_{i+1} - x_i)^2, smoothing / first differences; r = 2: Whittaker /
+    Hodrick-Prescott smoothing, curvature penalties -- the kind of objective whose Hessian the reference reaches only through hess_lag_vec!,
+    src/autodiff_generators.jl:72-107) under dense linear equalities, with the optional ball (slack variable) and box bounds of
+    :class:`QuadLinearBallBox`.  order = 1: the Lagrangian Hessian is TRIDIAGONAL: diagonal phi''(x_i) + kappa deg_i (+ 2 lam_ball; deg = 1 at
+    the two ends, 2 inside), couplings -kappa; ``optimize`` hands it to projcg_ as a :class:`TridiagonalOperator` (``offdiag`` below; with
+    bounds the augmented stacked diagonal next to the same couplings) and the truncated-Newton solves keep one pass over the basis per iteration
+    (lfpsqp_projcg_tridiag).  order >= 2: the Hessian is BANDED with bandwidth r (the diagonal and the r off-diagonals of kappa D^r'D^r,
+    :func:`difference_band`, built once on the host): ``offdiags`` (N x r device matrix) and a :class:`BandedOperator` on lfpsqp_projcg_band.
+    The slack row, when the ball is there, has no chain term.  One rank (the couplings would cross the shard boundaries)."""
+
+    def __init__(self, ctx: Context, n: int, m: int, Jct: DeviceMatrix, b, kind: int, a, c=0.0, kappa: float = 1.0, order: int = 1, **kw):
         assert kw.get("n_global", n) in (None, n), "chain objective: one rank (the couplings would cross the shard boundaries)"
+        assert int(order) in (1, 2, 3, 4), "chain objective: order 1 .. 4"
         super().__init__(ctx, n, m, Jct, b, kind, a, c, **kw)
-        from .projcg import TridiagonalOperator
+        from .projcg import BandedOperator, TridiagonalOperator
         self.kappa = float(kappa)
+        self.order = int(order)
         N = self.N                                                        # n, or n + 1 with the ball's slack variable (no chain term on it)
         deg = np.zeros(N)
-        deg[:n] = 2.0 * self.kappa
-        deg[0] = deg[n - 1] = self.kappa if n > 1 else 0.0
-        off = np.full(N, -self.kappa)
-        off[n - 1:] = 0.0                                                 # (entry n-1 would couple the last variable to the slack row; N-1 is ignored)
-        self._deg = ctx.vector(N, deg)
-        self.offdiag = ctx.vector(N, off)
-        self._lap = TridiagonalOperator(0.0, self._deg, self.offdiag)     # kappa * L, L = the path graph's Laplacian
+        if self.order == 1:
+            deg[:n] = 2.0 * self.kappa
+            deg[0] = deg[n - 1] = self.kappa if n > 1 else 0.0
+            off = np.full(N, -self.kappa)
+            off[n - 1:] = 0.0                                             # (entry n-1 would couple the last variable to the slack row; N-1 is ignored)
+            self._deg = ctx.vector(N, deg)
+            self.offdiag = ctx.vector(N, off)
+            self._lap = TridiagonalOperator(0.0, self._deg, self.offdiag)     # kappa * L, L = the path graph's Laplacian
+        else:
+            offs = np.zeros((N, self.order), order='F')
+            deg[:n], offs[:n] = difference_band(n, self.order, self.kappa)   # (entries i + k >= n are zero: no coupling to the slack row)
+            self._deg = ctx.vector(N, deg)
+            self.offdiags = ctx.matrix(N, self.order, offs)
+            self._lap = BandedOperator(0.0, self._deg, self.offdiags, self.order)    # kappa D'D
         self._tmp = ctx.vector(N)
         self._lap2 = self._tmp2 = None                                    # the same over stacked iterates [x | gap | y] (bounds): zero on the y half
 
     def _chain(self, x: DeviceVector):
-        """tmp = kappa L x (x plain, or stacked: the x half)."""
+        """tmp = kappa D'D x (x plain, or stacked: the x half)."""
         if x.n == self.N:
             return self._lap.mul_(self._tmp, x)
         if self._lap2 is None:
             from .inequality import StackedVector
-            from .projcg import TridiagonalOperator
+            from .projcg import BandedOperator, TridiagonalOperator
             deg2 = StackedVector(self.ctx, self.N)
             deg2.copy_range_from(self._deg, self.N)
-            self._lap2 = TridiagonalOperator(0.0, deg2, self.offdiag)
+            if self.order == 1:
+                self._lap2 = TridiagonalOperator(0.0, deg2, self.offdiag)
+            else:
+                self._lap2 = BandedOperator(0.0, deg2, self.offdiags, self.order)
             self._tmp2 = StackedVector(self.ctx, self.N)
         return self._lap2.mul_(self._tmp2, x)
 

@@ -126,6 +126,38 @@ class TridiagonalOperator:
         return self
 
 
+class BandedOperator:
+    """(A v)_i = (a0 + dg_i) v_i + sum_{k=1..bw} (off_k[i-k] v_{i-k} + off_k[i] v_{i+k}), 1 <= bw <= 4: a diagonal Hessian plus couplings up to
+    ``bw`` rows apart (second or higher differences: Whittaker / Hodrick-Prescott smoothing, curvature penalties).  ``off``: DeviceMatrix with n
+    rows and at least ``bw`` columns, column k-1 = off_k (entry i couples rows i and i+k; entries with i + k >= n are ignored).  On a
+    :class:`DeviceBasis` projcg_ runs it on the fused ONE-pass iteration (lfpsqp_projcg_band; bw = 1 is the tridiagonal path, bit for bit);
+    ``mul_`` is the operator on its own (lfpsqp_band_mul), which the generic loop / lfpsqp_projcg_op use -- two passes over the basis per
+    iteration.  ``fused = False`` sends projcg_ to that callback path.  With bounds (a stacked basis): ``dg`` is a :class:`StackedVector` and
+    ``off`` has N rows, the couplings of the x half, as for :class:`TridiagonalOperator`."""
+
+    def __init__(self, a0: float, dg: DeviceVector | None, off: DeviceMatrix, bw: int):
+        self.a0, self.dg, self.off, self.bw = float(a0), dg, off, int(bw)
+        self.fused = True
+        self._tmp = None
+
+    def _mul(self, ctx, v, out):
+        return ctx.L.lfpsqp_band_mul(ctx.h, self.a0, self.dg.h if self.dg is not None else None, self.off.h, self.bw, v.h, out.h)
+
+    def mul_(self, dest: DeviceVector, v: DeviceVector, a=None, b=None):
+        ctx = dest.ctx
+        if a is None:
+            ctx.check(self._mul(ctx, v, dest))
+            return dest
+        if self._tmp is None or self._tmp.n != dest.n:
+            self._tmp = DeviceVector(ctx, dest.n)
+        ctx.check(self._mul(ctx, v, self._tmp))
+        waxpby(a, self._tmp, b, dest, dest)
+        return dest
+
+    def adjoint(self):
+        return self
+
+
 class DeviceBasis:
     """Orthonormal U = Z[:, :ncols] (``view(U, :, 1:rank)``, src/optimize.jl:370).
     ``Z = None`` with ``generator = (A, W)``: the basis in FACTORED form U = A W -- never materialised; projcg_, the Newton retraction and
@@ -276,6 +308,19 @@ def projcg_(x: DeviceVector, lam: DeviceVector | None, A, U, b: DeviceVector, c:
         rc = ctx.L.lfpsqp_projcg_tridiag(ctx.h, x.h, lam.h if lam is not None else None, C.byref(a_c), work.Av.h, C.byref(u_c), b.h,
                                          c.h if c is not None else None, float(tol), int(maxit), int(n_global), flags,
                                          C.byref(w_c), C.byref(iters), C.byref(nr))
+        if rc != -5 or start_given:  # LFPSQP_ERR_UNSUPPORTED (no one-pass iteration for this shape / more than one rank): the callback path below
+            ctx.check(rc)
+            return iters.value, nr.value
+    if isinstance(A, BandedOperator) and (isinstance(U, DeviceBasis) or stacked) and not (resume or start_projected) and A.fused:
+        if getattr(work, "Av", None) is None:
+            work.Av = DeviceVector(ctx, n)
+        iters = _capi.c_i64()
+        nr = C.c_double()
+        u_c, w_c = U._c(), work._c()
+        flags = (WANT_LAMBDA if (want_lambda and lam is not None) else 0) | (START_GIVEN if start_given else 0)
+        rc = ctx.L.lfpsqp_projcg_band(ctx.h, x.h, lam.h if lam is not None else None, A.a0, A.dg.h if A.dg is not None else None, A.off.h,
+                                      A.bw, work.Av.h, C.byref(u_c), b.h, c.h if c is not None else None, float(tol), int(maxit),
+                                      int(n_global), flags, C.byref(w_c), C.byref(iters), C.byref(nr))
         if rc != -5 or start_given:  # LFPSQP_ERR_UNSUPPORTED (no one-pass iteration for this shape / more than one rank): the callback path below
             ctx.check(rc)
             return iters.value, nr.value
