@@ -204,6 +204,9 @@ __global__ __launch_bounds__(kThreads) void hash_mat_kernel(double* M, int64_t l
 //   kind 0: a (x-c)^2            kind 1: a (x-c)^4 + (x-c)^2            kind 2: a (sqrt(1 + (x-c)^2) - 1)   (pseudo-Huber)
 // mode 0: partial sums of phi; 1: out = phi'(x) ; 2: out = phi''(x) -- elementwise, no transcendental functions (the
 // same bits as a numpy evaluation up to the rounding of sqrt and the summation order).
+// kind 2, mode 0 is evaluated as a t^2 / (sqrt(1 + t^2) + 1): the same function, without the cancellation of s - 1 for small t (relative
+// error 2^-53 / t^2, exactly 0 for |t| <= 2^-27 -- the small residuals near a solution).  Every value is good to a few ulp RELATIVE for
+// |t| < 1e154 (t*t overflows beyond; tests/test_primitives_exact.py derives the counts).
 __device__ __forceinline__ double sep_eval(int kind, int mode, double a, double t) {   // t = x - c
     if (kind == 0) return mode == 0 ? a * t * t : (mode == 1 ? 2.0 * a * t : 2.0 * a);
     if (kind == 1) {
@@ -211,7 +214,7 @@ __device__ __forceinline__ double sep_eval(int kind, int mode, double a, double 
         return mode == 0 ? fma(a * t2, t2, t2) : (mode == 1 ? fma(4.0 * a * t2, t, 2.0 * t) : fma(12.0 * a, t2, 2.0));
     }
     const double s = sqrt(fma(t, t, 1.0));
-    return mode == 0 ? a * (s - 1.0) : (mode == 1 ? a * t / s : a / (s * s * s));
+    return mode == 0 ? a * t * t / (s + 1.0) : (mode == 1 ? a * t / s : a / (s * s * s));
 }
 struct SepF {
     int kind, mode;

@@ -34,6 +34,24 @@ class StackedVector(DeviceVector):
     def download2(self) -> np.ndarray:
         return np.concatenate([self.download(self.N, 0), self.download(self.N, self.hs)])
 
+    # The gap [N, hs) stays zero (include/lfpsqp_hip.h: the reductions run over the whole stacked length), so the two fills of
+    # DeviceVector, which write the whole allocation, are restated here on the two halves.
+    def fill(self, value: float):
+        if value == 0.0:                    # (zeros may go everywhere: one launch, as x.fill(0.0) at the start of every solve wants it)
+            return super().fill(value)
+        for off in (0, self.hs):
+            self.ctx.check(self.ctx.L.lfpsqp_vec_fill_range(self.ctx.h, self.h, off, self.N, float(value)))
+        return self
+
+    def hash_fill(self, seed: int, offset: int = 0, scale: float = 1.0, shift: float = 0.0):
+        """Logical entry k of [x; y] = scale * u(seed, offset + k) + shift, like a plain 2N-vector."""
+        tmp = DeviceVector(self.ctx, self.N)
+        for half, off in enumerate((0, self.hs)):
+            tmp.hash_fill(seed, offset + half * self.N, scale, shift)
+            self.copy_range_from(tmp, self.N, off, 0)
+        tmp.free()
+        return self
+
 
 class InequalityData:
     """InequalityData(xl, xu) (src/inequality_helper.jl:39-89), device-resident q, r, s, t."""

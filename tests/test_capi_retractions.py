@@ -772,7 +772,7 @@ def _sep_host(kind, a, c):
         t = x - c
         if kind == 0: return a * t * t
         if kind == 1: return a * t ** 4 + t * t
-        return a * (np.sqrt(1.0 + t * t) - 1.0)
+        return a * t * t / (np.sqrt(1.0 + t * t) + 1.0)           # (= a (sqrt(1 + t^2) - 1) without its cancellation: sep_eval's expression)
 
     def d1(x):
         t = x - c
