@@ -501,6 +501,26 @@ int lfpsqp_projcg_band(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, doubl
                        int64_t n_global, int flags, const lfpsqp_projcg_work* work, int64_t* iters, double* nr);
 int lfpsqp_band_mul(lfpsqp_ctx* ctx, double a0, const lfpsqp_vec* dg, const lfpsqp_mat* off, int64_t bw, const lfpsqp_vec* v, lfpsqp_vec* out);
 
+/* ... and for a GRID-STENCIL Hessian: a diagonal plus K = 1 .. 4 off-diagonals at ARBITRARY distances (a smoothness / diffusion term on a 2-D or
+ * 3-D field stored in row-major order: distances {1, nx} for the 5-point stencil, {1, nx, nx ny} for the 7-point one, {1, nx-1, nx, nx+1} for
+ * the 9-point one):
+ *     (A v)_i = (a0 + dg_i) v_i + sum_{k=1..K} ( off_k[i - s_k] v_{i - s_k} + off_k[i] v_{i + s_k} ),   1 <= s_1 < s_2 < ... < s_K < rows
+ * dist: the K distances (host).  off: a plain device matrix (no view) with at least K columns, column k-1 = off_k; off_k[i] couples rows i and
+ * i + s_k, entries with i + s_k >= its number of rows are ignored.  The ends of a grid line are expressed in the data (off_1[i] = 0 where i is the
+ * last point of a line), not in the operator.  Still ONE pass over U per iteration, and the pass is that of lfpsqp_projcg_tridiag; before it two
+ * vector kernels store A d and gather the neighbours' part of A rr at the shifted rows, and U'A U is formed once per solve by one shifted
+ * weighted Gram pass per off-diagonal (the distance a run-time argument), plus one or two.  Av, the basis shapes, the flags, the stacked form
+ * (off of N rows, the x half's couplings; dg stacked) and the refusals (LFPSQP_ERR_UNSUPPORTED: matrix view as basis, fewer than 4 or more
+ * than 1024 columns, a communicator, c != 0 with a stacked basis; RESUME / START_PROJECTED are argument errors) are those of lfpsqp_projcg_band.
+ * LFPSQP_ERR_ARG: K outside 1 .. 4, distances not strictly increasing, s_1 < 1, s_K >= rows, a view as off, dist == NULL.  Iterates, counts
+ * and exits as projcg! with A as a matrix (src/projcg.jl:40-121), to rounding; a solve is bit-reproducible per (n, m, distances).
+ * lfpsqp_diags_mul: out = A v (out != v), the operator on its own; it takes the same stacked pair (v, out stacked, off of N rows). */
+int lfpsqp_projcg_diags(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, double a0, const lfpsqp_vec* dg, const lfpsqp_mat* off, int64_t K,
+                        const int64_t* dist, lfpsqp_vec* Av, const lfpsqp_basis* U, const lfpsqp_vec* b, const lfpsqp_vec* c, double tol,
+                        int64_t maxit, int64_t n_global, int flags, const lfpsqp_projcg_work* work, int64_t* iters, double* nr);
+int lfpsqp_diags_mul(lfpsqp_ctx* ctx, double a0, const lfpsqp_vec* dg, const lfpsqp_mat* off, int64_t K, const int64_t* dist, const lfpsqp_vec* v,
+                     lfpsqp_vec* out);
+
 /* The same solver for a GENERAL symmetric operator A -- the reference's LinearMap closure around hess_lag_vec! /
  * augmented_hess_lag_vec! (src/optimize.jl:228-230, applied at src/projcg.jl:57,74,116): `A(user, src, dest)` must produce
  * dest = A * src for device vectors of length(b) (stacked [x | gap | y] when U is a stacked basis), return 0, and leave

@@ -241,6 +241,10 @@ c_projcg_band(ctx, x, lam, a0, dg, off, bw, Av, U, b, c, tol, maxit, nglob, flag
     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ref{CBasis}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Int64, Int64, Cint, Ref{CWork}, Ref{Int64}, Ref{Float64}),
     ctx, x, lam, a0, dg, off, bw, Av, U, b, c, tol, maxit, nglob, flags, work, iters, nr)
 c_band_mul(ctx, a0, dg, off, bw, v, out) = ccall((:lfpsqp_band_mul, lib), Cint, (Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}), ctx, a0, dg, off, bw, v, out)
+c_projcg_diags(ctx, x, lam, a0, dg, off, K, dist, Av, U, b, c, tol, maxit, nglob, flags, work, iters, nr) = ccall((:lfpsqp_projcg_diags, lib), Cint,
+    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Cvoid}, Ref{CBasis}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Int64, Int64, Cint, Ref{CWork}, Ref{Int64}, Ref{Float64}),
+    ctx, x, lam, a0, dg, off, K, dist, Av, U, b, c, tol, maxit, nglob, flags, work, iters, nr)
+c_diags_mul(ctx, a0, dg, off, K, dist, v, out) = ccall((:lfpsqp_diags_mul, lib), Cint, (Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Cvoid}, Ptr{Cvoid}), ctx, a0, dg, off, K, dist, v, out)
 c_projcg_op(ctx, x, lam, A, user, Av, U, b, c, tol, maxit, nglob, flags, work, iters, nr) = ccall((:lfpsqp_projcg_op, lib), Cint,
     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{CBasis}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Int64, Int64, Cint, Ref{CWork}, Ref{Int64}, Ref{Float64}),
     ctx, x, lam, A, user, Av, U, b, c, tol, maxit, nglob, flags, work, iters, nr)
@@ -612,6 +616,21 @@ function LinearAlgebra.mul!(dest::DeviceVector, A::BandedOperator, v::DeviceVect
     return dest
 end
 
+# (A v)_i = (a0 + dg_i) v_i + Σ_k (off_k[i-s_k] v_{i-s_k} + off_k[i] v_{i+s_k}) for 1 <= K <= 4 off-diagonals at ARBITRARY distances
+# dists = [s_1 < ... < s_K]: the stencil of a 2-D / 3-D grid in row-major order ([1, nx], [1, nx, nx*ny], [1, nx-1, nx, nx+1]).  off: an
+# n x (>= K) device matrix, column k = off_k (entries with i + s_k > n are ignored; the ends of a grid line are zeros in the data).  projcg! keeps
+# ONE pass over the basis per iteration with it (lfpsqp_projcg_diags); mul! is the LinearMap's action.
+struct DiagonalsOperator
+    a0::Float64
+    dg::Union{Nothing,DeviceVector}
+    off::DeviceMatrix
+    dists::Vector{Int64}
+end
+function LinearAlgebra.mul!(dest::DeviceVector, A::DiagonalsOperator, v::DeviceVector)
+    GC.@preserve A check(dest.ctx, c_diags_mul(dest.ctx.h, A.a0, A.dg === nothing ? C_NULL : A.dg.h, A.off.h, Int64(length(A.dists)), pointer(A.dists), v.h, dest.h))
+    return dest
+end
+
 # InequalityData(xl, xu) (src/inequality_helper.jl:39-89), device-resident q, r, s, t
 struct InequalityData
     q::DeviceVector
@@ -761,6 +780,21 @@ function projcg!(x::DeviceVector, λ::Union{Nothing,DeviceVector}, A::BandedOper
     rc = GC.@preserve U A c_projcg_band(x.ctx.h, x.h, λ === nothing ? C_NULL : λ.h, A.a0, A.dg === nothing ? C_NULL : A.dg.h, A.off.h, Int64(A.bw),
                                         Av.h, Ref(cbasis(U)), b.h, c === nothing ? C_NULL : c.h, tol, Int64(maxit), Int64(n_global), flags,
                                         Ref(cwork(work)), iters, nr)
+    if rc == LFPSQP_ERR_UNSUPPORTED && !start_given
+        return projcg!(x, λ, (dest, src) -> mul!(dest, A, src), U, b, c; tol=tol, maxit=maxit, work=work, n_global=n_global)
+    end
+    check(x.ctx, rc)
+    return Int(iters[]), nr[]
+end
+# Grid-stencil Hessian (off-diagonals at arbitrary distances): the same rules (lfpsqp_projcg_diags; A.off has N rows with a stacked basis)
+function projcg!(x::DeviceVector, λ::Union{Nothing,DeviceVector}, A::DiagonalsOperator, U::AnyBasis, b::DeviceVector, c::Union{Nothing,DeviceVector};
+                 tol::Float64=1e-6, maxit::Int=length(b) + ncols(U), work::ProjCGWork=ProjCGWork(x, ncols(U)), n_global::Int=length(b),
+                 Av::DeviceVector=DeviceVector(x.ctx, length(b)), start_given::Bool=false)
+    iters = Ref{Int64}(0); nr = Ref{Float64}(0.0)
+    flags = (λ === nothing ? Cint(0) : LFPSQP_PROJCG_WANT_LAMBDA) | (start_given ? LFPSQP_PROJCG_START_GIVEN : Cint(0))
+    rc = GC.@preserve U A c_projcg_diags(x.ctx.h, x.h, λ === nothing ? C_NULL : λ.h, A.a0, A.dg === nothing ? C_NULL : A.dg.h, A.off.h,
+                                         Int64(length(A.dists)), pointer(A.dists), Av.h, Ref(cbasis(U)), b.h, c === nothing ? C_NULL : c.h, tol,
+                                         Int64(maxit), Int64(n_global), flags, Ref(cwork(work)), iters, nr)
     if rc == LFPSQP_ERR_UNSUPPORTED && !start_given
         return projcg!(x, λ, (dest, src) -> mul!(dest, A, src), U, b, c; tol=tol, maxit=maxit, work=work, n_global=n_global)
     end
@@ -1422,6 +1456,9 @@ hess_offdiag(h) = nothing
 # A BANDED one (bandwidth 2 .. 4): hess_band(problem) returns an N x bw device matrix (column k couples variables i and i+k) or nothing; the
 # truncated-Newton solves then run projcg! with a BandedOperator under the same rules.
 hess_band(h) = nothing
+# A GRID-STENCIL one (a 2-D / 3-D field with a smoothness term): hess_diagonals(problem) returns (dists, off) -- up to four distances and an N x K
+# device matrix (column k couples variables i and i + dists[k]) -- or nothing; projcg! with a DiagonalsOperator under the same rules.
+hess_diagonals(h) = nothing
 
 function optimize_core(ctx::HipContext, f, grad!, c!, jac!, hess_lag_vec!, x0::Vector{Float64}, xl, xu, m::Int, param::LFPSQPParams=LFPSQPParams();
                        n_global::Int=length(x0))
@@ -1460,7 +1497,7 @@ function optimize_core(ctx::HipContext, f, grad!, c!, jac!, hess_lag_vec!, x0::V
     # (the library says whether this context can run projcg! without Z for this Jct: one-pass kernels on, shape inside their limits, or a
     # sparse twin the nonzero path covers; otherwise Z is materialised and every path has its two-pass form)
     # (a tridiagonal Hessian sent through the callback path -- DeviceOptions.tridiagonal_one_pass off -- needs the materialised basis)
-    tri_callback = diagonal_hessian && (hess_offdiag(hess_lag_vec!) !== nothing || hess_band(hess_lag_vec!) !== nothing) && !ctx.options.tridiagonal_one_pass
+    tri_callback = diagonal_hessian && (hess_offdiag(hess_lag_vec!) !== nothing || hess_band(hess_lag_vec!) !== nothing || hess_diagonals(hess_lag_vec!) !== nothing) && !ctx.options.tridiagonal_one_pass
     factored_basis = ctx.options.factored_basis && diagonal_hessian && !tri_callback && 4 <= m <= 1024 && factored_basis_supported(ctx, Jct, jsp === nothing ? C_NULL : jsp.h)
     # allocation by trial pays after several hundred projected-CG iterations; a Lagrangian Hessian that is a multiple of I (config 3) ends every
     # truncated-Newton solve after one: such a run takes its first allocations
@@ -1489,7 +1526,8 @@ function optimize_core(ctx::HipContext, f, grad!, c!, jac!, hess_lag_vec!, x0::V
     fuse_tangent = factored_basis && param.do_newton && jsp === nothing && m > 0 && ctx.options.fused_tangent_step && !(ineq && nonlinear_class)
     tri_off = diagonal_hessian ? hess_offdiag(hess_lag_vec!) : nothing
     band_off = (diagonal_hessian && tri_off === nothing) ? hess_band(hess_lag_vec!) : nothing
-    if tri_off !== nothing || band_off !== nothing           # (with bounds: the augmented stacked diagonal next to the same couplings)
+    diags_off = (diagonal_hessian && tri_off === nothing && band_off === nothing) ? hess_diagonals(hess_lag_vec!) : nothing
+    if tri_off !== nothing || band_off !== nothing || diags_off !== nothing           # (with bounds: the augmented stacked diagonal next to the same couplings)
         ctx.options.tridiagonal_one_pass || (fuse_tangent = false)     # (the callback path starts its solves itself)
         (haskey(VIEW_KEEP, Jct) || ctx.nranks > 1) && (fuse_tangent = false)  # (lfpsqp_projcg_tridiag refuses a matrix view / several ranks: callback path, its own start)
     end                                                       # (the tangent step still hands projcg! r0 and U'r0; never its folded initial projection)
@@ -1585,7 +1623,7 @@ function optimize_core(ctx::HipContext, f, grad!, c!, jac!, hess_lag_vec!, x0::V
                     hess_diag!(hess_lag_vec!, hdst, x, λ_kkt)
                 end
                 # the fold of projcg!'s initial projection: only where the Gram matrix resolves I - U'U (full rank, cond^2 <= 10)
-                init_fold = tri_off === nothing && band_off === nothing && rank == m && Σ[1]^2 <= 10.0 * Σ[m]^2
+                init_fold = tri_off === nothing && band_off === nothing && diags_off === nothing && rank == m && Σ[1]^2 <= 10.0 * Σ[m]^2
                 GC.@preserve Ub cons_part begin
                     cref = cons_part === nothing ? nothing : Ref(ccons(cons_part))
                     iref = ineq ? Ref(cineq(idata)) : nothing
@@ -1658,6 +1696,15 @@ function optimize_core(ctx::HipContext, f, grad!, c!, jac!, hess_lag_vec!, x0::V
                                                   work=projcgwork, n_global=nglob, start_given=fused_now)
                     else
                         tn_iter, tn_res = projcg!(newton_d, nothing, (dest, src) -> mul!(dest, Aband, src), Qview, d, nothing; tol=tol,
+                                                  maxit=param.tn_maxiter, work=projcgwork, n_global=nglob)
+                    end
+                elseif diags_off !== nothing
+                    Adiags = DiagonalsOperator(0.0, a_diag, diags_off[2], collect(Int64, diags_off[1]))
+                    if ctx.options.tridiagonal_one_pass
+                        tn_iter, tn_res = projcg!(newton_d, nothing, Adiags, Qview, d, nothing; tol=tol, maxit=param.tn_maxiter,
+                                                  work=projcgwork, n_global=nglob, start_given=fused_now)
+                    else
+                        tn_iter, tn_res = projcg!(newton_d, nothing, (dest, src) -> mul!(dest, Adiags, src), Qview, d, nothing; tol=tol,
                                                   maxit=param.tn_maxiter, work=projcgwork, n_global=nglob)
                     end
                 else
@@ -1992,7 +2039,7 @@ optimize(ctx::HipContext, f, grad!, c!, jac_c!, d!, jac_d!, hess_lag_vec!, x0::V
 
 export HipContext, HipError, DeviceOptions, DeviceVector, StackedVector, DeviceMatrix, SparseMatrix, spmv_t!, spmv_n!, to_dense!, DeviceBasis, DiagOperator, LowRankOperator, InequalityData, InequalityDecomp,
        InequalityDecompProject, ProjCGWork, DeviceConstraints, NR, ProjPenalty, ProjPenaltyWork, Euclidean, YRetract, ArmijoWork,
-       ExactLinesearchWork, LFPSQPParams, TerminationInfo, QuadLinearBallBox, SeparableLinearBallBox, ChainSeparableLinear, TridiagonalOperator, BandedOperator, SeparableElementwiseBox, ElementwiseConstraints,
+       ExactLinesearchWork, LFPSQPParams, TerminationInfo, QuadLinearBallBox, SeparableLinearBallBox, ChainSeparableLinear, TridiagonalOperator, BandedOperator, DiagonalsOperator, SeparableElementwiseBox, ElementwiseConstraints,
        sin_system_constraints, sphere_system_constraints, clone, rowscale!, set_placement!, basis_and_vectors_placed, vectors_placed, placement_info, upload!, download, upload2!, download2, projcg!, retract!,
        retract_nr_batch!, pcg!, ProjPrecondition, ksvd!, armijo!, exact_linesearch!, optimize, optimize_core, hess_diag!, jac!, comm_unique_id, comm_init!, comm_p2p_export, comm_init_p2p!,
        shard_range, sync

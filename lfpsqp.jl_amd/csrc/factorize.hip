@@ -48,13 +48,18 @@ constexpr int kTLd = 17;
 // formed in registers on the way to LDS.  k = 1: one more scalar load per column and step (the row below a lane's pair; same cache line but for one
 // lane in eight); k even: one aligned pair load of rows kh + k, kh + k + 1; k odd > 1: two scalar loads.  This is the Gram matrix behind the
 // reduced operator of a banded Hessian (lfpsqp_projcg_tridiag / lfpsqp_projcg_band: U'A U = sum_k R_k'|off_k| R_k + U' diag(c) U).
+// SHIFT = -1: the same operand with a RUN-TIME distance s >= 1 (the off-diagonals of a grid stencil, lfpsqp_projcg_diags; s arrives in `xoff`, which
+// a shifted launch does not need: it carries no extra columns): rows kh + s, kh + s + 1 by one aligned pair load for even s, two scalar loads for
+// odd s, zero from row n on.  For a far distance the partner rows are not in the lines the workgroup loads next: such a pass streams M twice.
 template <bool DIAG, bool WEIGHTED, int SHIFT = 0, int NX = 0>
 __global__ __launch_bounds__(kThreads, 2) void gram_kernel(const double* __restrict__ M, int64_t ld, int64_t n, int ncols, int npan,
                                                          int ngroups, const double* __restrict__ w2, double* __restrict__ part,
                                                          int64_t part_ld, const double* __restrict__ ex0, const double* __restrict__ ex1,
                                                          int64_t xoff, const double* __restrict__ sgn) {
     static_assert(SHIFT == 0 || WEIGHTED, "the shifted operand exists for weighted launches only");
-    static_assert(SHIFT >= 0 && SHIFT <= 4, "shift distances 1 .. 4");
+    static_assert(SHIFT >= -1 && SHIFT <= 4, "shift distances 1 .. 4, or -1: the distance at run time");
+    constexpr bool RT = SHIFT < 0;                      // run-time distance
+    constexpr bool PAIR = SHIFT > 1 || RT;              // the partner rows are a pair of their own
     // NX: how many of the extra right-hand columns (ex0, then ex1) this launch carries -- a compile-time fact: as run-time null tests of two
     // pointers the columns' multiply-adds were if-converted into 32 FMAs and ~37 compares / selects per two steps of EVERY launch, more vector
     // instructions than the rest of the loop has, between the matrix-core instructions of a wave (FINDINGS.md 12.8)
@@ -94,7 +99,7 @@ __global__ __launch_bounds__(kThreads, 2) void gram_kernel(const double* __restr
     // buffer is staged, so that no arithmetic waits on the loads in flight.
     double2 va[DEPTH][4], vb[needB ? DEPTH : 1][4], vw[WEIGHTED ? DEPTH : 1];
     // SHIFT: the partner rows of the columns -- k = 1: row kh + 2 (row kh + 1 is the pair's own); else rows kh + k, kh + k + 1
-    using ZT = std::conditional_t<(SHIFT > 1), double2, double>;
+    using ZT = std::conditional_t<PAIR, double2, double>;
     ZT za[SHIFT ? DEPTH : 1][SHIFT ? 4 : 1], zb[(SHIFT && needB) ? DEPTH : 1][(SHIFT && needB) ? 4 : 1];
     double2 vs[SHIFT ? DEPTH : 1];
     double2 ve[2] = {make_double2(0.0, 0.0), make_double2(0.0, 0.0)};      // the extra columns' entries of the rows kh, kh + 1 of the step in flight
@@ -145,12 +150,16 @@ __global__ __launch_bounds__(kThreads, 2) void gram_kernel(const double* __restr
                     if (below && (FULL || 32 * q < nb)) zb[buf][q] = pb[r + q * cs + 2];
                 }
             }
-        } else if constexpr (SHIFT > 1) {
+        } else if constexpr (PAIR) {
             vs[buf] = ld2(sgn + r + kh);
             // rows kh + k, kh + k + 1: zero from row n on (and there may lie outside the allocation); the pair load where both exist
-            const bool b1 = r + kh + SHIFT < n, b2 = r + kh + SHIFT + 1 < n;
+            const int64_t sh = RT ? xoff : (int64_t)SHIFT;
+            const bool b1 = r + kh + sh < n, b2 = r + kh + sh + 1 < n;
             auto partner = [&](const double* p) -> double2 {
-                if constexpr (SHIFT % 2 == 0) {
+                if constexpr (RT) {
+                    if ((sh & 1) == 0 && b2) return ld2(p + sh);
+                    return make_double2(b1 ? p[sh] : 0.0, b2 ? p[sh + 1] : 0.0);
+                } else if constexpr (SHIFT % 2 == 0) {
                     if (b2) return ld2(p + SHIFT);
                     return make_double2(b1 ? p[SHIFT] : 0.0, 0.0);
                 } else {
@@ -173,7 +182,7 @@ __global__ __launch_bounds__(kThreads, 2) void gram_kernel(const double* __restr
         for (int q = 0; q < 4; ++q) {
             double2 a = va[buf][q];
             if constexpr (SHIFT == 1) a = make_double2(fma(vs[buf].x, a.y, a.x), fma(vs[buf].y, za[buf][q], a.y));
-            if constexpr (SHIFT > 1) a = make_double2(fma(vs[buf].x, za[buf][q].x, a.x), fma(vs[buf].y, za[buf][q].y, a.y));
+            if constexpr (PAIR) a = make_double2(fma(vs[buf].x, za[buf][q].x, a.x), fma(vs[buf].y, za[buf][q].y, a.y));
             if constexpr (WEIGHTED) { a.x *= vw[buf].x; a.y *= vw[buf].y; }
             As[p][c + 32 * q][kh] = a.x;
             As[p][c + 32 * q][kh + 1] = a.y;
@@ -184,7 +193,7 @@ __global__ __launch_bounds__(kThreads, 2) void gram_kernel(const double* __restr
             if constexpr (needB) {
                 double2 b = vb[buf][q];
                 if constexpr (SHIFT == 1) b = make_double2(fma(vs[buf].x, b.y, b.x), fma(vs[buf].y, zb[buf][q], b.y));
-                if constexpr (SHIFT > 1) b = make_double2(fma(vs[buf].x, zb[buf][q].x, b.x), fma(vs[buf].y, zb[buf][q].y, b.y));
+                if constexpr (PAIR) b = make_double2(fma(vs[buf].x, zb[buf][q].x, b.x), fma(vs[buf].y, zb[buf][q].y, b.y));
                 if constexpr (WEIGHTED) { b.x *= vw[buf].x; b.y *= vw[buf].y; }
                 Bs[p][c + 32 * q][kh] = b.x;
                 Bs[p][c + 32 * q][kh + 1] = b.y;
@@ -646,10 +655,11 @@ struct SqrtWTimesV {
 };
 
 static int gram_impl(lfpsqp_ctx* ctx, const lfpsqp_mat* M, int ncols_all, const double* w2, std::vector<double>& G, const GramRhs* rhs = nullptr,
-                     const double* shift_sgn = nullptr, int shift = 1) {
-    // shift_sgn != NULL: the Gram matrix of R, R_i = M_i + shift_sgn_i M_{i+shift} (gram_kernel SHIFT) -- plain matrix, weights given, no extra columns
-    if (shift_sgn && (M->view || !w2 || rhs || shift < 1 || shift > 4))
-        return set_err(ctx, LFPSQP_ERR_ARG, "shifted Gram matrix: plain matrix with weights, no right-hand columns, shift 1 .. 4");
+                     const double* shift_sgn = nullptr, int64_t shift = 1) {
+    // shift_sgn != NULL: the Gram matrix of R, R_i = M_i + shift_sgn_i M_{i+shift} (gram_kernel SHIFT; a distance above 4 goes to the run-time
+    // instantiation) -- plain matrix, weights given, no extra columns
+    if (shift_sgn && (M->view || !w2 || rhs || shift < 1))
+        return set_err(ctx, LFPSQP_ERR_ARG, "shifted Gram matrix: plain matrix with weights, no right-hand columns, shift >= 1");
     G.assign((size_t)ncols_all * ncols_all, 0.0);
     const int nxu = rhs ? rhs->nx : 0;
     if (rhs && rhs->X) rhs->X->assign((size_t)ncols_all * nxu, 0.0);
@@ -773,15 +783,17 @@ static int gram_impl(lfpsqp_ctx* ctx, const lfpsqp_mat* M, int ncols_all, const 
         if (shift_sgn) {
             auto launch_shifted = [&](auto Kc) {
                 constexpr int K = decltype(Kc)::value;
-                hipLaunchKernelGGL((gram_kernel<true, true, K>), dim3(gd * npan), dim3(kThreads), 0, ctx->stream, M->p, M->ld, M->n, ncols, npan, gd, sw, ctx->part, pld, nullptr, nullptr, pp, shift_sgn);
+                const int64_t xo = K < 0 ? shift : pp;        // (the run-time distance travels in the extra columns' offset, which no shifted launch uses)
+                hipLaunchKernelGGL((gram_kernel<true, true, K>), dim3(gd * npan), dim3(kThreads), 0, ctx->stream, M->p, M->ld, M->n, ncols, npan, gd, sw, ctx->part, pld, nullptr, nullptr, xo, shift_sgn);
                 if (noff > 0)
-                    hipLaunchKernelGGL((gram_kernel<false, true, K>), dim3(go * noff), dim3(kThreads), 0, ctx->stream, M->p, M->ld, M->n, ncols, npan, go, sw, ctx->part, pld, nullptr, nullptr, pp, shift_sgn);
+                    hipLaunchKernelGGL((gram_kernel<false, true, K>), dim3(go * noff), dim3(kThreads), 0, ctx->stream, M->p, M->ld, M->n, ncols, npan, go, sw, ctx->part, pld, nullptr, nullptr, xo, shift_sgn);
             };
             switch (shift) {
                 case 1: launch_shifted(std::integral_constant<int, 1>{}); break;
                 case 2: launch_shifted(std::integral_constant<int, 2>{}); break;
                 case 3: launch_shifted(std::integral_constant<int, 3>{}); break;
-                default: launch_shifted(std::integral_constant<int, 4>{}); break;
+                case 4: launch_shifted(std::integral_constant<int, 4>{}); break;
+                default: launch_shifted(std::integral_constant<int, -1>{}); break;
             }
         } else {
             if (nslots == 2) hipLaunchKernelGGL((gram_kernel<true, true, false, 2>), dim3(gd * npan), dim3(kThreads), 0, ctx->stream, M->p, M->ld, M->n, ncols, npan, gd, sw, ctx->part, pld, ex0, ex1, pp, nullptr);
@@ -1313,7 +1325,7 @@ static int check_weights(lfpsqp_ctx* ctx, bool weighted, const std::vector<doubl
 }
 
 // G (ncols x ncols, column-major) = R' diag(w) R for R_i = M_i + sgn_i M_{i+shift} (w >= 0 and sgn = +-1: device n-vectors; projcg.hip)
-int lfpsqp::gram_shifted(lfpsqp_ctx* ctx, const lfpsqp_mat* M, int ncols, const double* w, const double* sgn, std::vector<double>& G, int shift) {
+int lfpsqp::gram_shifted(lfpsqp_ctx* ctx, const lfpsqp_mat* M, int ncols, const double* w, const double* sgn, std::vector<double>& G, int64_t shift) {
     LF_TRY(gram_impl(ctx, M, ncols, w, G, nullptr, sgn, shift));
     return check_weights(ctx, true, G);
 }

@@ -358,6 +358,128 @@ struct TriPrepSF {
     }
 };
 
+// A = a0*I + diag(dg) + K (1 .. 4) off-diagonals at RUN-TIME distances 1 <= s_1 < ... < s_K < nc -- the stencil of a 2-D / 3-D grid stored in
+// row-major order ({1, nx}, {1, nx, nx ny}, {1, nx - 1, nx, nx + 1}); lfpsqp_projcg_diags / lfpsqp_diags_mul:
+//     (A v)_i = (a0 + dg_i) v_i + sum_k ( off_k[i - s_k] v_{i - s_k} + off_k[i] v_{i + s_k} )
+// (off_k[i] couples rows i and i + s_k; entries with i + s_k >= nc are ignored).  Stacked vectors as for BandD: couplings on the first nc rows.
+// The neighbours are plain gathers: within a wave they are as coalesced as the rows themselves; whether they come from the L2 (near
+// distances) or from further away (a grid line or plane apart) is the memory system's business, not the kernel's.
+struct DiagsD {
+    double a0;
+    const double* dg;
+    const double* off;        // coupling column k (0 .. K - 1) at off + k * ldo
+    int64_t ldo;
+    int64_t n;
+    int64_t nc;
+    int K;
+    int64_t s[4];
+    __device__ __forceinline__ const double* col(int k) const { return off + (int64_t)k * ldo; }
+    // row j < nc of the off-diagonal part applied to the vector whose entry r is src(r): per distance the lower, then the upper coupling
+    template <class SRC>
+    __device__ __forceinline__ double couple(int64_t j, double o, SRC&& src) const {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (k >= K) break;
+            const double* ok = col(k);
+            const int64_t sk = s[k];
+            if (j >= sk) o = fma(ok[j - sk], src(j - sk), o);
+            if (j + sk < nc) o = fma(ok[j], src(j + sk), o);
+        }
+        return o;
+    }
+};
+struct DiagsMulF {   // out = A v
+    DiagsD A;
+    const double* v;
+    double* out;
+    const int64_t* istat;     // nullptr: always; else only while the solve is running
+    __device__ __forceinline__ bool skip() const { return istat != nullptr && ld_stat(istat + I_STATUS) != ST_RUNNING; }
+    __device__ __forceinline__ double row(int64_t j, double vj, double dj) const {
+        const double o = (A.a0 + dj) * vj;
+        if (j >= A.nc) return o;
+        return A.couple(j, o, [&](int64_t r) { return v[r]; });
+    }
+    __device__ __forceinline__ void apply(int64_t i, bool v0, bool v1, double*) const {
+        if (!v0) return;
+        const double2 vv = ld2(v + i);
+        const double2 dd = A.dg ? ld2(A.dg + i) : make_double2(0.0, 0.0);
+        const double o0 = row(i, vv.x, dd.x);
+        if (!v1) { out[i] = o0; return; }
+        st2(out + i, make_double2(o0, row(i + 1, vv.y, dd.y)));
+    }
+};
+// What TriPrepF gives the fused iteration (PcgFuseTri), for far neighbours: no register window reaches them, so  ad = A d  is stored first
+// (DiagsMulF, while the solve runs) and this kernel gathers  q_i = sum_k (off_k[i-s_k] rr_{i-s_k} + off_k[i] rr_{i+s_k})  from
+// rr = g + alpha ad at the shifted rows (the same fma as the pass forms for its own row).  ad == nullptr: rr = g as stored -- the initial
+// residual (INIT), or the projected residual ux that DiagsPrepSF left for a stacked basis.
+struct DiagsGatherF {
+    DiagsD A;                 // n = nc = the rows with couplings
+    const double* g;
+    const double* ad;
+    double* q;
+    const double* scal;
+    const int64_t* istat;
+    __device__ __forceinline__ bool skip() const { return ld_stat(istat + I_STATUS) != ST_RUNNING; }
+    __device__ __forceinline__ void apply(int64_t i, bool v0, bool v1, double*) const {
+        if (!v0) return;
+        double q0, q1 = 0.0;
+        if (ad) {
+            const double alpha = ld_scal(scal + S_ALPHA);
+            auto rr = [&](int64_t r) { return fma(alpha, ad[r], g[r]); };                 // :93
+            q0 = A.couple(i, 0.0, rr);
+            if (v1) q1 = A.couple(i + 1, 0.0, rr);
+        } else {
+            auto rr = [&](int64_t r) { return g[r]; };
+            q0 = A.couple(i, 0.0, rr);
+            if (v1) q1 = A.couple(i + 1, 0.0, rr);
+        }
+        if (v1) st2(q + i, make_double2(q0, q1));
+        else q[i] = q0;
+    }
+};
+// Stacked basis (PcgFuseTri<true, .>), the row-local half of TriPrepSF:  ad = (T d)_x  and the x half of the residual projected off the diagonal
+// block,  ux_r = rx_r - Dx_r (Dx_r rx_r + Dy_r ry_r)  with  rr = g + alpha A d  (the pass's own expressions), stored once so that DiagsGatherF can
+// gather it at the far rows.  INIT: rr is the stored initial residual, only ux is written.
+template <bool INIT>
+struct DiagsPrepSF {
+    DiagsD A;                 // n = nc = N; dg stacked (the y half at dg + hs)
+    int64_t hs;
+    const double *Dx, *Dy;
+    const double* g;
+    const double* d;
+    double* ad;
+    double* ux;
+    const double* scal;
+    const int64_t* istat;
+    __device__ __forceinline__ bool skip() const { return ld_stat(istat + I_STATUS) != ST_RUNNING; }
+    __device__ __forceinline__ double row(int64_t j, double alpha, double& a) const {
+        double rx = g[j], ry = g[hs + j];
+        a = 0.0;
+        if (!INIT) {
+            const double ax = A.a0 + (A.dg ? A.dg[j] : 0.0), ay = A.a0 + (A.dg ? A.dg[hs + j] : 0.0);
+            a = A.couple(j, ax * d[j], [&](int64_t r) { return d[r]; });
+            rx = fma(alpha, a, rx);                                              // :93
+            ry = fma(alpha, ay * d[hs + j], ry);
+        }
+        const double ww = Dx[j] * rx + Dy[j] * ry;
+        return rx - Dx[j] * ww;
+    }
+    __device__ __forceinline__ void apply(int64_t i, bool v0, bool v1, double*) const {
+        if (!v0) return;
+        const double alpha = INIT ? 0.0 : ld_scal(scal + S_ALPHA);
+        double a0v, a1v = 0.0;
+        const double u0 = row(i, alpha, a0v);
+        if (v1) {
+            const double u1 = row(i + 1, alpha, a1v);
+            st2(ux + i, make_double2(u0, u1));
+            if (!INIT) st2(ad + i, make_double2(a0v, a1v));
+        } else {
+            ux[i] = u0;
+            if (!INIT) ad[i] = a0v;
+        }
+    }
+};
+
 // ---- K1 -----------------------------------------------------------------------
 struct PcgDirF {
     double* d;
@@ -1309,6 +1431,45 @@ __global__ __launch_bounds__(256) void tri_stack_weights_kernel(BandD<B> A, int6
         for (int k = 1; k <= B; ++k) aoff[(k - 1) * npad + i] = (i + k < A.n) ? sx[i] * A.col(k)[i] * sx[i + k] : 0.0;
     }
 }
+// the same two kernels for off-diagonals at run-time distances (DiagsD, lfpsqp_projcg_diags)
+__global__ __launch_bounds__(256) void diags_weights_kernel(DiagsD A, double* __restrict__ wabs /* K columns, npad apart */, double* __restrict__ sgn,
+                                                            double* __restrict__ cpos, double* __restrict__ cneg, int64_t npad, double* __restrict__ anyneg) {
+    bool neg = false;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < npad; i += (int64_t)gridDim.x * 256) {
+        double cp = 0.0, cn = 0.0;
+        double c = (i < A.n) ? A.a0 + (A.dg ? A.dg[i] : 0.0) : 0.0;
+        for (int k = 0; k < A.K; ++k) {
+            double wa = 0.0, sg = 1.0;
+            if (i < A.n) {
+                const double o = (i + A.s[k] < A.n) ? A.col(k)[i] : 0.0;
+                wa = fabs(o);
+                sg = (o < 0.0) ? -1.0 : 1.0;
+                const double wm = (i >= A.s[k]) ? fabs(A.col(k)[i - A.s[k]]) : 0.0;
+                c = c - wa - wm;
+            }
+            wabs[k * npad + i] = wa; sgn[k * npad + i] = sg;
+        }
+        if (i < A.n) {
+            if (c >= 0.0) cp = c;
+            else { cn = -c; neg = true; }
+            if (c != c) cp = c;                               // (NaN data: let the Gram pass report it)
+        }
+        cpos[i] = cp; cneg[i] = cn;
+    }
+    if (neg) *anyneg = 1.0;
+}
+__global__ __launch_bounds__(256) void diags_stack_weights_kernel(DiagsD A, int64_t hs, const double* __restrict__ sx, const double* __restrict__ sy,
+                                                                  double* __restrict__ adg, double* __restrict__ aoff /* K columns, npad apart */, int64_t npad) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < npad; i += (int64_t)gridDim.x * 256) {
+        double dv = 0.0;
+        if (i < A.n) {
+            const double ax = A.a0 + (A.dg ? A.dg[i] : 0.0), ay = A.a0 + (A.dg ? A.dg[hs + i] : 0.0);
+            dv = fma(sx[i] * sx[i], ax, sy[i] * sy[i] * ay);
+        }
+        adg[i] = dv;
+        for (int k = 0; k < A.K; ++k) aoff[k * npad + i] = (i + A.s[k] < A.n) ? sx[i] * A.col(k)[i] * sx[i + A.s[k]] : 0.0;
+    }
+}
 static int ensure_tri(lfpsqp_ctx* ctx, size_t doubles) {
     if (doubles <= ctx->tri_cap) return 0;
     LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1319,48 +1480,49 @@ static int ensure_tri(lfpsqp_ctx* ctx, size_t doubles) {
     ctx->tri_cap = doubles;
     return 0;
 }
-// Mh (m x m, column-major, host) = U'A U for U = Z[:, :mc] (W == nullptr, m == mc) or U = Z[:, :mc] W (W: mc x m, host); sk: a stacked basis,
-// U = [sx; sy] .* (that), and A over the x half (A.n = N rows, dg stacked)
-template <int B>
-static int tri_reduced_operator(lfpsqp_ctx* ctx, const lfpsqp_mat* Z, int mc, const BandD<B>& A0, const double* W, int m, std::vector<double>& Mh,
-                                const StackD* sk = nullptr) {
-    const int64_t n = A0.n, npad = round_up((n > 0 ? n : 1) + 1, kPadRows);
-    LF_TRY(ensure_tri(ctx, (2 * B + 2 + (sk ? 1 + B : 0)) * (size_t)npad + 8));
-    double* wabs = ctx->d_tri;
-    double* sgn = wabs + B * npad;
-    double* cpos = sgn + B * npad;
-    double* cneg = cpos + npad;
-    double* anyneg = cneg + npad;
-    BandD<B> A = A0;
-    const unsigned nblk = (unsigned)std::min<int64_t>((npad + 255) / 256, 4096);
-    if (sk) {
-        double* adg = anyneg + 8;
-        double* aoff = adg + npad;
-        hipLaunchKernelGGL(tri_stack_weights_kernel<B>, dim3(nblk), dim3(256), 0, ctx->stream, A0, sk->hs, sk->sx, sk->sy, adg, aoff, npad);
-        LF_LAUNCH_CHECK(ctx);
-        A = BandD<B>{0.0, adg, aoff, npad, n, n};
-    }
-    LF_HIP(ctx, hipMemsetAsync(anyneg, 0, sizeof(double), ctx->stream));
-    hipLaunchKernelGGL(tri_weights_kernel<B>, dim3(nblk), dim3(256), 0, ctx->stream, A, wabs, sgn, cpos, cneg, npad, anyneg);
-    LF_LAUNCH_CHECK(ctx);
+// the set-up vectors of the reduced operator in ctx->d_tri: K columns of |off| and of sign(off), the two parts of the diagonal weights, a flag;
+// stacked: the diagonal and the K coupling columns of At behind them
+struct TriWeights {
+    int64_t npad;
+    double *wabs, *sgn, *cpos, *cneg, *anyneg, *adg, *aoff;
+    unsigned nblk;
+};
+static int tri_weights_alloc(lfpsqp_ctx* ctx, int64_t n, int K, bool stacked, TriWeights& w) {
+    w.npad = round_up((n > 0 ? n : 1) + 1, kPadRows);
+    LF_TRY(ensure_tri(ctx, (2 * K + 2 + (stacked ? 1 + K : 0)) * (size_t)w.npad + 8));
+    w.wabs = ctx->d_tri;
+    w.sgn = w.wabs + K * w.npad;
+    w.cpos = w.sgn + K * w.npad;
+    w.cneg = w.cpos + w.npad;
+    w.anyneg = w.cneg + w.npad;
+    w.adg = w.anyneg + 8;
+    w.aoff = w.adg + w.npad;
+    w.nblk = (unsigned)std::min<int64_t>((w.npad + 255) / 256, 4096);
+    return 0;
+}
+// Mh = sum_k R_k' diag(|off_k|) R_k + Z' diag(cpos) Z - Z' diag(cneg) Z from the prepared weights (dist[k]: the row distance of column k), then
+// W'(.)W for a basis in factored form
+static int reduced_from_weights(lfpsqp_ctx* ctx, const lfpsqp_mat* Z, int mc, int64_t n, int K, const int64_t* dist, const TriWeights& w,
+                                const double* W, int m, std::vector<double>& Mh) {
+    const int64_t npad = w.npad;
     double hneg = 0.0;
-    LF_HIP(ctx, hipMemcpyAsync(&hneg, anyneg, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    LF_HIP(ctx, hipMemcpyAsync(&hneg, w.anyneg, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const lfpsqp_mat Zp = Z->plain();
     std::vector<double> G, G2((size_t)mc * mc);
-    LF_TRY(gram_shifted(ctx, &Zp, mc, wabs, sgn, G, 1));
-    for (int k = 2; k <= B; ++k) {
-        LF_TRY(gram_shifted(ctx, &Zp, mc, wabs + (k - 1) * npad, sgn + (k - 1) * npad, G2, k));
+    LF_TRY(gram_shifted(ctx, &Zp, mc, w.wabs, w.sgn, G, dist[0]));
+    for (int k = 2; k <= K; ++k) {
+        LF_TRY(gram_shifted(ctx, &Zp, mc, w.wabs + (k - 1) * npad, w.sgn + (k - 1) * npad, G2, dist[k - 1]));
         for (size_t e = 0; e < G.size(); ++e) G[e] += G2[e];
     }
     G2.resize((size_t)mc * mc);
     lfpsqp_vec wv;
     wv.n = n; wv.cap = npad;
-    wv.p = cpos;
+    wv.p = w.cpos;
     LF_TRY(lfpsqp_gram(ctx, &Zp, mc, &wv, G2.data()));
     for (size_t k = 0; k < G.size(); ++k) G[k] += G2[k];
     if (hneg != 0.0) {
-        wv.p = cneg;
+        wv.p = w.cneg;
         LF_TRY(lfpsqp_gram(ctx, &Zp, mc, &wv, G2.data()));
         for (size_t k = 0; k < G.size(); ++k) G[k] -= G2[k];
     }
@@ -1382,6 +1544,43 @@ static int tri_reduced_operator(lfpsqp_ctx* ctx, const lfpsqp_mat* Z, int mc, co
         }
     return 0;
 }
+// Mh (m x m, column-major, host) = U'A U for U = Z[:, :mc] (W == nullptr, m == mc) or U = Z[:, :mc] W (W: mc x m, host); sk: a stacked basis,
+// U = [sx; sy] .* (that), and A over the x half (A.n = N rows, dg stacked)
+template <int B>
+static int tri_reduced_operator(lfpsqp_ctx* ctx, const lfpsqp_mat* Z, int mc, const BandD<B>& A0, const double* W, int m, std::vector<double>& Mh,
+                                const StackD* sk = nullptr) {
+    const int64_t n = A0.n;
+    TriWeights w;
+    LF_TRY(tri_weights_alloc(ctx, n, B, sk != nullptr, w));
+    BandD<B> A = A0;
+    if (sk) {
+        hipLaunchKernelGGL(tri_stack_weights_kernel<B>, dim3(w.nblk), dim3(256), 0, ctx->stream, A0, sk->hs, sk->sx, sk->sy, w.adg, w.aoff, w.npad);
+        LF_LAUNCH_CHECK(ctx);
+        A = BandD<B>{0.0, w.adg, w.aoff, w.npad, n, n};
+    }
+    LF_HIP(ctx, hipMemsetAsync(w.anyneg, 0, sizeof(double), ctx->stream));
+    hipLaunchKernelGGL(tri_weights_kernel<B>, dim3(w.nblk), dim3(256), 0, ctx->stream, A, w.wabs, w.sgn, w.cpos, w.cneg, w.npad, w.anyneg);
+    LF_LAUNCH_CHECK(ctx);
+    const int64_t dist[4] = {1, 2, 3, 4};
+    return reduced_from_weights(ctx, Z, mc, n, B, dist, w, W, m, Mh);
+}
+// ... for off-diagonals at run-time distances (A0.n = A0.nc = the rows of Z)
+static int diags_reduced_operator(lfpsqp_ctx* ctx, const lfpsqp_mat* Z, int mc, const DiagsD& A0, const double* W, int m, std::vector<double>& Mh,
+                                  const StackD* sk = nullptr) {
+    const int64_t n = A0.n;
+    TriWeights w;
+    LF_TRY(tri_weights_alloc(ctx, n, A0.K, sk != nullptr, w));
+    DiagsD A = A0;
+    if (sk) {
+        hipLaunchKernelGGL(diags_stack_weights_kernel, dim3(w.nblk), dim3(256), 0, ctx->stream, A0, sk->hs, sk->sx, sk->sy, w.adg, w.aoff, w.npad);
+        LF_LAUNCH_CHECK(ctx);
+        A.a0 = 0.0; A.dg = w.adg; A.off = w.aoff; A.ldo = w.npad;
+    }
+    LF_HIP(ctx, hipMemsetAsync(w.anyneg, 0, sizeof(double), ctx->stream));
+    hipLaunchKernelGGL(diags_weights_kernel, dim3(w.nblk), dim3(256), 0, ctx->stream, A, w.wabs, w.sgn, w.cpos, w.cneg, w.npad, w.anyneg);
+    LF_LAUNCH_CHECK(ctx);
+    return reduced_from_weights(ctx, Z, mc, n, A0.K, A0.s, w, W, m, Mh);
+}
 
 // the banded operator of lfpsqp_projcg_tridiag (bw = 1, off a vector) and lfpsqp_projcg_band (off a plain matrix): bw coupling columns of `rows`
 // entries, ld apart
@@ -1390,7 +1589,11 @@ struct BandOp {
     const lfpsqp_vec* dg;
     const double* off;
     int64_t ld, rows;
-    int bw;
+    int bw;                   // 0: off-diagonals at the K run-time distances below (lfpsqp_projcg_diags)
+    int K = 0;
+    int64_t dist[4] = {0, 0, 0, 0};
+    // over vectors of n rows, couplings on the first nc
+    DiagsD diags(const double* dgp, int64_t n, int64_t nc) const { return DiagsD{a0, dgp, off, ld, n, nc, K, {dist[0], dist[1], dist[2], dist[3]}}; }
 };
 // fn(std::integral_constant<int, B>) for B = bw (1 .. 4)
 template <typename F>
@@ -1515,12 +1718,13 @@ static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const
     const double* tri_dg = (TRop && TRop->dg) ? TRop->dg->p : nullptr;
     if (TRop) {
         // (stacked: dg over both halves, off the x half's couplings -- N rows; the y half is diagonal)
-        LF_ARG(ctx, TRop->off && TRop->rows == N && TRop->bw >= 1 && TRop->bw <= 4 && (!TRop->dg || TRop->dg->n == nv));
+        LF_ARG(ctx, TRop->off && TRop->rows == N && TRop->bw >= 0 && TRop->bw <= 4 && (!TRop->dg || TRop->dg->n == nv));
         if (!fused || !plain_mat(Z) || ctx->comm_active())
             return set_err(ctx, LFPSQP_ERR_UNSUPPORTED, "%s: needs the one-pass iteration over a dense basis (4 .. 1024 columns, no matrix "
                                                         "view) on a single rank (the couplings would cross the shard boundaries); use lfpsqp_projcg_op",
-                           TRop->bw == 1 ? "lfpsqp_projcg_tridiag" : "lfpsqp_projcg_band");
-        LF_TRY(with_band(TRop->bw, [&](auto Bc) -> int {
+                           TRop->bw == 0 ? "lfpsqp_projcg_diags" : (TRop->bw == 1 ? "lfpsqp_projcg_tridiag" : "lfpsqp_projcg_band"));
+        if (TRop->bw == 0) LF_TRY(diags_reduced_operator(ctx, Z, mc, TRop->diags(tri_dg, N, N), DF ? U->W : nullptr, m, triMh, stacked ? &sk : nullptr));
+        else LF_TRY(with_band(TRop->bw, [&](auto Bc) -> int {
             constexpr int B = decltype(Bc)::value;
             return tri_reduced_operator<B>(ctx, Z, mc, BandD<B>{TRop->a0, tri_dg, TRop->off, TRop->ld, N, N}, DF ? U->W : nullptr, m, triMh,
                                            stacked ? &sk : nullptr);
@@ -1588,7 +1792,8 @@ static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const
             return residual_with(AOpLR{Ad.a0, Ad.dg, LRop->V->p, LRop->V->ld, kLR, lrSig, lrVtv}, sgn, store, t_out);
         }
         if (TRop) {                                                           // Av = A x by the stencil kernel, then as a stored product
-            LF_TRY(with_band(TRop->bw, [&](auto Bc) -> int {
+            if (TRop->bw == 0) LF_TRY((run_vec<DiagsMulF, 0, NoPost>(ctx, nv, DiagsMulF{TRop->diags(tri_dg, nv, N), x->p, Av->p, nullptr}, 0u, nullptr, NoPost())));
+            else LF_TRY(with_band(TRop->bw, [&](auto Bc) -> int {
                 constexpr int B = decltype(Bc)::value;
                 const BandD<B> Am{TRop->a0, tri_dg, TRop->off, TRop->ld, nv, N};
                 return run_vec<TriMulF<B>, 0, NoPost>(ctx, nv, TriMulF<B>{Am, x->p, Av->p, nullptr}, 0u, nullptr, NoPost());
@@ -1645,7 +1850,28 @@ static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const
         double* Tout = DF ? Traw : T12;
         // tridiagonal / banded: the neighbours' contributions first (a vector kernel), into Av while rp still holds the initial residual, into rp
         // afterwards (stacked: both into the first N entries).  The pass itself does not depend on the bandwidth.
-        if (TRop) {
+        if (TRop && TRop->bw == 0) {
+            // off-diagonals at run-time distances: A d stored first, then the gather of the neighbours' rr (stacked: of ux, kept in the set-up's
+            // scratch, which is free once M is on the device); the same four passes
+            const DiagsD Ab = TRop->diags(tri_dg, N, N);
+            double* ux = ctx->d_tri;
+            if (stacked && init) {
+                LF_TRY((run_vec<DiagsPrepSF<true>, 0, NoPost>(ctx, N, DiagsPrepSF<true>{Ab, hs, sk.Dx, sk.Dy, rp, nullptr, nullptr, ux, scal, istat}, 0u, nullptr, NoPost())));
+                LF_TRY((run_vec<DiagsGatherF, 0, NoPost>(ctx, N, DiagsGatherF{Ab, ux, nullptr, Av->p, scal, istat}, 0u, nullptr, NoPost())));
+                LF_TRY((run_onepass<PcgFuseTri<true, true>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseTri<true, true>{rp, gin, gout, d, nullptr, Av->p, Ad, scal, istat, sk}, Tout, slot)));
+            } else if (stacked) {
+                LF_TRY((run_vec<DiagsPrepSF<false>, 0, NoPost>(ctx, N, DiagsPrepSF<false>{Ab, hs, sk.Dx, sk.Dy, gin, d, Av->p, ux, scal, istat}, 0u, nullptr, NoPost())));
+                LF_TRY((run_vec<DiagsGatherF, 0, NoPost>(ctx, N, DiagsGatherF{Ab, ux, nullptr, rp, scal, istat}, 0u, nullptr, NoPost())));
+                LF_TRY((run_onepass<PcgFuseTri<true, false>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseTri<true, false>{rp, gin, gout, d, Av->p, rp, Ad, scal, istat, sk}, Tout, slot)));
+            } else if (init) {
+                LF_TRY((run_vec<DiagsGatherF, 0, NoPost>(ctx, nv, DiagsGatherF{Ab, rp, nullptr, Av->p, scal, istat}, 0u, nullptr, NoPost())));
+                LF_TRY((run_onepass<PcgFuseTri<false, true>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseTri<false, true>{rp, gin, gout, d, nullptr, Av->p, Ad, scal, istat, sk}, Tout, slot)));
+            } else {
+                LF_TRY((run_vec<DiagsMulF, 0, NoPost>(ctx, nv, DiagsMulF{Ab, d, Av->p, istat}, 0u, nullptr, NoPost())));
+                LF_TRY((run_vec<DiagsGatherF, 0, NoPost>(ctx, nv, DiagsGatherF{Ab, gin, Av->p, rp, scal, istat}, 0u, nullptr, NoPost())));
+                LF_TRY((run_onepass<PcgFuseTri<false, false>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseTri<false, false>{rp, gin, gout, d, Av->p, rp, Ad, scal, istat, sk}, Tout, slot)));
+            }
+        } else if (TRop) {
             LF_TRY(with_band(TRop->bw, [&](auto Bc) -> int {
                 constexpr int B = decltype(Bc)::value;
                 const BandD<B> Ab{TRop->a0, tri_dg, TRop->off, TRop->ld, N, N};
@@ -1907,6 +2133,40 @@ extern "C" int lfpsqp_tridiag_mul(lfpsqp_ctx* ctx, const lfpsqp_tridiag_op* A, c
 extern "C" int lfpsqp_band_mul(lfpsqp_ctx* ctx, double a0, const lfpsqp_vec* dg, const lfpsqp_mat* off, int64_t bw, const lfpsqp_vec* v, lfpsqp_vec* out) {
     LF_ARG(ctx, ctx && off && plain_mat(off) && bw >= 1 && bw <= 4 && off->m >= bw);
     return band_mul(ctx, "lfpsqp_band_mul", a0, dg, off->p, off->ld, off->n, (int)bw, v, out);
+}
+
+// the off-diagonals of lfpsqp_projcg_diags / lfpsqp_diags_mul: K (1 .. 4) columns of a plain matrix, strictly increasing distances in 1 .. rows - 1
+static int diags_op(lfpsqp_ctx* ctx, double a0, const lfpsqp_vec* dg, const lfpsqp_mat* off, int64_t K, const int64_t* dist, BandOp& bop) {
+    LF_ARG(ctx, off && plain_mat(off) && dist && K >= 1 && K <= 4 && off->m >= K);
+    bop = BandOp{a0, dg, off->p, off->ld, off->n, 0};
+    bop.K = (int)K;
+    for (int k = 0; k < K; ++k) {
+        LF_ARG(ctx, dist[k] >= 1 && dist[k] < off->n && (k == 0 || dist[k] > dist[k - 1]));
+        bop.dist[k] = dist[k];
+    }
+    return 0;
+}
+
+extern "C" int lfpsqp_projcg_diags(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, double a0, const lfpsqp_vec* dg, const lfpsqp_mat* off, int64_t K,
+                                   const int64_t* dist, lfpsqp_vec* Av, const lfpsqp_basis* U, const lfpsqp_vec* b, const lfpsqp_vec* c, double tol,
+                                   int64_t maxit, int64_t n_global, int flags, const lfpsqp_projcg_work* work, int64_t* iters, double* nr) {
+    LF_RANGE("lfpsqp_projcg_diags");
+    LF_ARG(ctx, ctx && Av);
+    BandOp bop;
+    LF_TRY(diags_op(ctx, a0, dg, off, K, dist, bop));
+    return projcg_impl(ctx, x, lambda, nullptr, nullptr, nullptr, Av, U, b, c, tol, maxit, n_global, flags, work, iters, nr, nullptr, &bop);
+}
+
+extern "C" int lfpsqp_diags_mul(lfpsqp_ctx* ctx, double a0, const lfpsqp_vec* dg, const lfpsqp_mat* off, int64_t K, const int64_t* dist,
+                                const lfpsqp_vec* v, lfpsqp_vec* out) {
+    LF_ARG(ctx, ctx);
+    BandOp bop;
+    LF_TRY(diags_op(ctx, a0, dg, off, K, dist, bop));
+    LF_ARG(ctx, v && out && v != out && v->p != out->p && out->n == v->n && (!dg || dg->n == v->n));
+    LF_ARG(ctx, bop.rows == v->n || v->n == lfpsqp_half_stride(bop.rows) + bop.rows);
+    if (ctx->comm_active())
+        return set_err(ctx, LFPSQP_ERR_UNSUPPORTED, "lfpsqp_diags_mul: one rank only (no halo exchange between row shards)");
+    return run_vec<DiagsMulF, 0, NoPost>(ctx, v->n, DiagsMulF{bop.diags(dg ? dg->p : nullptr, v->n, bop.rows), v->p, out->p, nullptr}, 0u, nullptr, NoPost());
 }
 
 extern "C" int lfpsqp_projcg_op(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, lfpsqp_opfun A, void* user, lfpsqp_vec* Av,

@@ -184,7 +184,8 @@ def optimize_core(f, grad_, c_, jac_, hess_lag_vec_, x0, xl, xu, m: int, param: 
     # their limits, or a sparse twin the nonzero path covers); where it cannot (LFPSQP_ONEPASS=-1, ld beyond the 32-bit lane offsets ...)
     # Z is materialised and every path has its two-pass form.
     # (a tridiagonal or banded Hessian sent through the callback path -- DeviceOptions.tridiagonal_one_pass off -- needs the materialised basis)
-    coupled_hessian = diagonal_hessian and (getattr(hess_lag_vec_, "offdiag", None) is not None or getattr(hess_lag_vec_, "offdiags", None) is not None)
+    coupled_hessian = diagonal_hessian and (getattr(hess_lag_vec_, "offdiag", None) is not None or getattr(hess_lag_vec_, "offdiags", None) is not None
+                                            or getattr(hess_lag_vec_, "diagonals", None) is not None)
     tri_callback = coupled_hessian and not bool(getattr(ctx.options, "tridiagonal_one_pass", True))
     factored = (bool(ctx.options.factored_basis) and diagonal_hessian and not tri_callback and 4 <= m <= 1024
                 and ctx.factored_basis_supported(Jct, getattr(c_, "Jsp", None)))
@@ -221,7 +222,10 @@ def optimize_core(f, grad_, c_, jac_, hess_lag_vec_, x0, xl, xu, m: int, param: 
     # variables i and i+k: the same rules, lfpsqp_projcg_band
     tri_off = getattr(hess_lag_vec_, "offdiag", None) if diagonal_hessian else None
     band_off = getattr(hess_lag_vec_, "offdiags", None) if (diagonal_hessian and tri_off is None) else None
-    if tri_off is not None or band_off is not None:
+    # A GRID-STENCIL one (a 2-D / 3-D field with a smoothness term) exposes ``diagonals`` = (dists, off): up to four off-diagonals at arbitrary
+    # distances, off an N x K device matrix whose column k-1 couples variables i and i + dists[k-1]: the same rules, lfpsqp_projcg_diags
+    diags_off = getattr(hess_lag_vec_, "diagonals", None) if (diagonal_hessian and tri_off is None and band_off is None) else None
+    if tri_off is not None or band_off is not None or diags_off is not None:
         # (the tangent step's pass still hands projcg_ r0 and U'r0 -- neither involves A --, but never its folded initial projection, whose
         # sums are formed with the diagonal alone: init_fold stays off below)
         if not bool(getattr(ctx.options, "tridiagonal_one_pass", True)):
@@ -240,6 +244,11 @@ def optimize_core(f, grad_, c_, jac_, hess_lag_vec_, x0, xl, xu, m: int, param: 
         from .projcg import BandedOperator
         a_diag = projcgwork.placed_extra[0] if projcgwork.placed_extra else newvec()
         newton_map = BandedOperator(0.0, a_diag, band_off, band_off.m)
+        newton_map.fused = bool(getattr(ctx.options, "tridiagonal_one_pass", True))
+    elif diags_off is not None:
+        from .projcg import DiagonalsOperator
+        a_diag = projcgwork.placed_extra[0] if projcgwork.placed_extra else newvec()
+        newton_map = DiagonalsOperator(0.0, a_diag, diags_off[1], diags_off[0])
         newton_map.fused = bool(getattr(ctx.options, "tridiagonal_one_pass", True))
     elif diagonal_hessian:
         a_diag = projcgwork.placed_extra[0] if projcgwork.placed_extra else newvec()
@@ -341,7 +350,7 @@ def optimize_core(f, grad_, c_, jac_, hess_lag_vec_, x0, xl, xu, m: int, param: 
                 # (flag 1 = LFPSQP_TANGENT_INIT_PROJCG: the pass is projcg!'s initial projection as well -- src/projcg.jl:58-62 -- with U'r0 from
                 # the Gram matrix; projcg_ then starts with its first iteration, start_projected=True.  Only where the Gram matrix resolves
                 # I - U'U: a full-rank block with cond^2 <= 10, the fast path of the factorisation; otherwise projcg_ measures U'r0 itself)
-                init_fold = bool(tri_off is None and band_off is None and rank == m and S_[0] * S_[0] <= 10.0 * S_[m - 1] * S_[m - 1])
+                init_fold = bool(tri_off is None and band_off is None and diags_off is None and rank == m and S_[0] * S_[0] <= 10.0 * S_[m - 1] * S_[m - 1])
                 ctx.check(ctx.L.lfpsqp_tangent_step(ctx.h, C.byref(bs), sig_c.ctypes.data, vt_c.ctypes.data, m, Jtd.ctypes.data, Ggram.ctypes.data, d.h,
                                                     C.byref(cc) if cc is not None else None, x.h, a_diag.h,
                                                     C.byref(idc) if ineq else None, hx.h if ineq else None, idecomp.S.h if ineq else None,

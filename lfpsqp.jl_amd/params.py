@@ -108,5 +108,6 @@ class DeviceOptions:
     # iteration (lfpsqp_projcg_tridiag: U'AU by two or three Gram passes per solve, then 1.85 instead of 3.3 ms per iteration at (1e7, 128) -- ahead
     # from six to nine iterations per solve on; with bounds the stacked form of the same pass).  False: the same operator through the callback path
     # (lfpsqp_projcg_op), identical iterates.  The same switch governs a BANDED Hessian (an ``offdiags`` matrix next to ``diag_``, bandwidth up to 4:
-    # lfpsqp_projcg_band, one Gram pass per off-diagonal per solve on top)
+    # lfpsqp_projcg_band, one Gram pass per off-diagonal per solve on top) and a GRID-STENCIL one (``diagonals`` = (dists, off), up to four
+    # off-diagonals at arbitrary distances: lfpsqp_projcg_diags).
     tridiagonal_one_pass: bool = True

@@ -253,6 +253,92 @@ class ChainSeparableLinear(SeparableLinearBallBox):
         axpby(1.0, self._deg, 1.0, hx)
 
 
+def grid_laplacian(shape, kappa: float = 1.0):
+    """kappa L for the grid graph of a 2-D or 3-D field stored in row-major order (last axis fastest), L = D - W its Laplacian (edges between
+    neighbours along each axis): returns ``(diag, off, dists)`` -- the diagonal kappa deg_i (length n = prod(shape)), the couplings (n x K,
+    column k: entry i couples points i and i + dists[k]; -kappa on an edge, 0 where i is the last point along that axis) and the distances
+    (1, n_last, n_last n_mid ...) in increasing order; axes of length 1 have no edges and no column."""
+    shape = tuple(int(s) for s in shape)
+    assert len(shape) in (2, 3) and all(s >= 1 for s in shape)
+    n = int(np.prod(shape))
+    idx = np.arange(n).reshape(shape)
+    diag = np.zeros(n)
+    cols, dists = [], []
+    stride = 1
+    for ax in range(len(shape) - 1, -1, -1):                    # last axis first: increasing distances
+        if shape[ax] > 1:
+            lo = np.take(idx, np.arange(shape[ax] - 1), axis=ax).ravel()     # the points with a neighbour further along this axis
+            col = np.zeros(n)
+            col[lo] = -kappa
+            diag[lo] += kappa
+            diag[lo + stride] += kappa
+            cols.append(col)
+            dists.append(stride)
+        stride *= shape[ax]
+    assert cols, "grid_laplacian: a grid of more than one point"
+    return diag, np.asfortranarray(np.stack(cols, axis=1)), tuple(dists)
+
+
+class GridSeparableLinear(SeparableLinearBallBox):
+    """A separable objective plus a GRID smoothness term: f(x) = sum_i phi(x_i - c_i; a_i) + kappa/2 sum_{grid edges (i,j)} (x_i - x_j)^2 over a
+    2-D or 3-D field of ``shape`` in row-major order (an image, a volume: diffusion / Tikhonov smoothing) under dense linear equalities, with the
+    optional ball (slack variable) and box bounds of :class:`QuadLinearBallBox`.  The Lagrangian Hessian is a diagonal, phi''(x_i) + kappa deg_i
+    (+ 2 lam_ball), plus one off-diagonal per axis FAR from the main one (distances 1, nx, nx ny: :func:`grid_laplacian`): ``diagonals`` =
+    (dists, off) below, and ``optimize`` hands it to projcg_ as a :class:`DiagonalsOperator` -- the truncated-Newton solves keep one pass over
+    the basis per iteration (lfpsqp_projcg_diags; with bounds the augmented stacked diagonal next to the same couplings).  The slack row, when
+    the ball is there, has no couplings.  One rank (the couplings would cross the shard boundaries)."""
+
+    def __init__(self, ctx: Context, shape, m: int, Jct: DeviceMatrix, b, kind: int, a, c=0.0, kappa: float = 1.0, **kw):
+        n = int(np.prod(shape))
+        assert kw.get("n_global", n) in (None, n), "grid objective: one rank (the couplings would cross the shard boundaries)"
+        super().__init__(ctx, n, m, Jct, b, kind, a, c, **kw)
+        from .projcg import DiagonalsOperator
+        self.shape = tuple(int(s) for s in shape)
+        self.kappa = float(kappa)
+        N = self.N                                                        # n, or n + 1 with the ball's slack variable (no coupling to it)
+        deg_h, off_h, dists = grid_laplacian(self.shape, self.kappa)
+        deg = np.zeros(N)
+        off = np.zeros((N, len(dists)), order='F')
+        deg[:n], off[:n] = deg_h, off_h
+        self._deg = ctx.vector(N, deg)
+        self.diagonals = (dists, ctx.matrix(N, len(dists), off))
+        self._lap = DiagonalsOperator(0.0, self._deg, self.diagonals[1], dists)      # kappa L
+        self._tmp = ctx.vector(N)
+        self._lap2 = self._tmp2 = None                                    # the same over stacked iterates [x | gap | y] (bounds): zero on the y half
+
+    def _smooth(self, x: DeviceVector):
+        """tmp = kappa L x (x plain, or stacked: the x half)."""
+        if x.n == self.N:
+            return self._lap.mul_(self._tmp, x)
+        if self._lap2 is None:
+            from .inequality import StackedVector
+            from .projcg import DiagonalsOperator
+            deg2 = StackedVector(self.ctx, self.N)
+            deg2.copy_range_from(self._deg, self.N)
+            self._lap2 = DiagonalsOperator(0.0, deg2, self.diagonals[1], self.diagonals[0])
+            self._tmp2 = StackedVector(self.ctx, self.N)
+        return self._lap2.mul_(self._tmp2, x)
+
+    def f(self, x: DeviceVector) -> float:
+        from .device import dot
+        return super().f(x) + 0.5 * dot(x, self._smooth(x))
+
+    def grad_(self, g: DeviceVector, x: DeviceVector):
+        from .device import axpby
+        super().grad_(g, x)
+        axpby(1.0, self._smooth(x), 1.0, g)
+
+    def diag_objective_(self, hx: DeviceVector, x: DeviceVector):
+        from .device import axpby
+        super().diag_objective_(hx, x)
+        axpby(1.0, self._deg, 1.0, hx)
+
+    def diag_(self, hx: DeviceVector, x: DeviceVector, lam: np.ndarray):
+        from .device import axpby
+        super().diag_(hx, x, lam)
+        axpby(1.0, self._deg, 1.0, hx)
+
+
 class SeparableElementwiseBox(SeparableLinearBallBox):
     """The device-resident problem class with NONLINEAR equality constraints: a separable objective
     (``kind`` / ``a`` / ``c`` as in :class:`SeparableLinearBallBox`) under ``cons``, an :class:`ElementwiseConstraints`

@@ -158,6 +158,42 @@ class BandedOperator:
         return self
 
 
+class DiagonalsOperator:
+    """(A v)_i = (a0 + dg_i) v_i + sum_k (off_k[i - s_k] v_{i - s_k} + off_k[i] v_{i + s_k}) for 1 <= K <= 4 off-diagonals at ARBITRARY distances
+    ``dists`` = (s_1 < ... < s_K): the Hessian of a smoothness / diffusion term on a 2-D or 3-D field in row-major order ((1, nx), (1, nx, nx ny),
+    (1, nx - 1, nx, nx + 1) for the 5-, 7- and 9-point stencils; :func:`lfpsqp_jl_amd.problems.grid_laplacian`).  ``off``: DeviceMatrix with n
+    rows and at least K columns, column k-1 = off_k (entry i couples rows i and i + s_k; entries with i + s_k >= n are ignored; the ends of a
+    grid line are zeros in the data).  On a :class:`DeviceBasis` projcg_ runs it on the fused ONE-pass iteration (lfpsqp_projcg_diags);
+    ``mul_`` is the operator on its own (lfpsqp_diags_mul), which the generic loop / lfpsqp_projcg_op use -- two passes over the basis per
+    iteration.  ``fused = False`` sends projcg_ to that callback path.  With bounds (a stacked basis): ``dg`` is a :class:`StackedVector` and
+    ``off`` has N rows, the couplings of the x half, as for :class:`BandedOperator`."""
+
+    def __init__(self, a0: float, dg: DeviceVector | None, off: DeviceMatrix, dists):
+        self.a0, self.dg, self.off = float(a0), dg, off
+        self.dists = tuple(int(s) for s in dists)
+        self._dist_c = (_capi.c_i64 * max(len(self.dists), 1))(*self.dists)
+        self.fused = True
+        self._tmp = None
+
+    def _mul(self, ctx, v, out):
+        return ctx.L.lfpsqp_diags_mul(ctx.h, self.a0, self.dg.h if self.dg is not None else None, self.off.h, len(self.dists), self._dist_c,
+                                      v.h, out.h)
+
+    def mul_(self, dest: DeviceVector, v: DeviceVector, a=None, b=None):
+        ctx = dest.ctx
+        if a is None:
+            ctx.check(self._mul(ctx, v, dest))
+            return dest
+        if self._tmp is None or self._tmp.n != dest.n:
+            self._tmp = DeviceVector(ctx, dest.n)
+        ctx.check(self._mul(ctx, v, self._tmp))
+        waxpby(a, self._tmp, b, dest, dest)
+        return dest
+
+    def adjoint(self):
+        return self
+
+
 class DeviceBasis:
     """Orthonormal U = Z[:, :ncols] (``view(U, :, 1:rank)``, src/optimize.jl:370).
     ``Z = None`` with ``generator = (A, W)``: the basis in FACTORED form U = A W -- never materialised; projcg_, the Newton retraction and
@@ -321,6 +357,19 @@ def projcg_(x: DeviceVector, lam: DeviceVector | None, A, U, b: DeviceVector, c:
         rc = ctx.L.lfpsqp_projcg_band(ctx.h, x.h, lam.h if lam is not None else None, A.a0, A.dg.h if A.dg is not None else None, A.off.h,
                                       A.bw, work.Av.h, C.byref(u_c), b.h, c.h if c is not None else None, float(tol), int(maxit),
                                       int(n_global), flags, C.byref(w_c), C.byref(iters), C.byref(nr))
+        if rc != -5 or start_given:  # LFPSQP_ERR_UNSUPPORTED (no one-pass iteration for this shape / more than one rank): the callback path below
+            ctx.check(rc)
+            return iters.value, nr.value
+    if isinstance(A, DiagonalsOperator) and (isinstance(U, DeviceBasis) or stacked) and not (resume or start_projected) and A.fused:
+        if getattr(work, "Av", None) is None:
+            work.Av = DeviceVector(ctx, n)
+        iters = _capi.c_i64()
+        nr = C.c_double()
+        u_c, w_c = U._c(), work._c()
+        flags = (WANT_LAMBDA if (want_lambda and lam is not None) else 0) | (START_GIVEN if start_given else 0)
+        rc = ctx.L.lfpsqp_projcg_diags(ctx.h, x.h, lam.h if lam is not None else None, A.a0, A.dg.h if A.dg is not None else None, A.off.h,
+                                       len(A.dists), A._dist_c, work.Av.h, C.byref(u_c), b.h, c.h if c is not None else None, float(tol),
+                                       int(maxit), int(n_global), flags, C.byref(w_c), C.byref(iters), C.byref(nr))
         if rc != -5 or start_given:  # LFPSQP_ERR_UNSUPPORTED (no one-pass iteration for this shape / more than one rank): the callback path below
             ctx.check(rc)
             return iters.value, nr.value
