@@ -149,6 +149,30 @@ struct BandWin {
             o[2 * p + 1] = x.y;
         }
     }
+    // near the two ends: entry r of a vector of n rows, zero outside the matrix (clamped index + select: no divergent loads)
+    static __device__ __forceinline__ double at(const double* v, int64_t n, int64_t r) {
+        const int64_t rc = r < 0 ? 0 : (r >= n ? n - 1 : r);
+        const double x = v[rc];
+        return (r == rc) ? x : 0.0;
+    }
+    static __device__ __forceinline__ double cpl(const BandD<B>& A, int k, int64_t r) {      // off_k[r] couples rows r and r + k: 0 <= r < n - k
+        const int64_t rc = r < 0 ? 0 : (r >= A.n ? A.n - 1 : r);
+        const double x = A.col(k)[rc];
+        return (r >= 0 && r + k < A.n) ? x : 0.0;
+    }
+    // the windows of the B coupling columns, interior (near the ends the kernels fill them entry by entry with cpl: the same loop moved in here
+    // compiles to different code)
+    static __device__ __forceinline__ void cpl_pairs(const BandD<B>& A, int64_t i, double (&o)[B][W]) {
+#pragma unroll
+        for (int k = 0; k < B; ++k) pairs(A.col(k + 1), i, o[k]);
+    }
+    // the neighbours' part of row r0 + t of A u:  sum_k (off_k[r - k] u_{r-k} + off_k[r] u_{r+k})
+    static __device__ __forceinline__ double neighbours(const double (&o)[B][W], const double (&u)[W], int t) {
+        double s = fma(o[0][t], u[t + 1], o[0][t - 1] * u[t - 1]);
+#pragma unroll
+        for (int k = 2; k <= B; ++k) s = fma(o[k - 1][t], u[t + k], fma(o[k - 1][t - k], u[t - k], s));
+        return s;
+    }
 };
 
 // What the fused banded iteration (PcgFuseTri) needs from the rows' NEIGHBOURS, as two stored vectors, so that the pass itself is row-local
@@ -168,25 +192,14 @@ struct TriPrepF {
     using Win = BandWin<B>;
     static constexpr int W = Win::W, L = Win::L, H = Win::H;
     __device__ __forceinline__ bool skip() const { return ld_stat(istat + I_STATUS) != ST_RUNNING; }
-    // entry r of a vector / of the couplings, zero outside the matrix (clamped index + select: no divergent loads)
-    __device__ __forceinline__ double at(const double* v, int64_t r) const {
-        const int64_t rc = r < 0 ? 0 : (r >= A.n ? A.n - 1 : r);
-        const double x = v[rc];
-        return (r == rc) ? x : 0.0;
-    }
-    __device__ __forceinline__ double cpl(int k, int64_t r) const {      // off_k[r] couples rows r and r + k: 0 <= r < n - k
-        const int64_t rc = r < 0 ? 0 : (r >= A.n ? A.n - 1 : r);
-        const double x = A.col(k)[rc];
-        return (r >= 0 && r + k < A.n) ? x : 0.0;
-    }
+    __device__ __forceinline__ double at(const double* v, int64_t r) const { return Win::at(v, A.n, r); }
     __device__ __forceinline__ void apply(int64_t i, bool v0, bool v1, double*) const {
         if (!v0) return;
         const double alpha = INIT ? 0.0 : ld_scal(scal + S_ALPHA);
         const int64_t r0 = i - 2 * B;                                            // row of window entry 0
         double o[B][W], gv[W], dv[W], axv[W], rr[W], adv[W];
         if (i >= 2 * B && i + 2 * B + 2 < A.n) {                                 // interior (all but the first and the last threads): aligned pair loads
-#pragma unroll
-            for (int k = 0; k < B; ++k) Win::pairs(A.col(k + 1), i, o[k]);
+            Win::cpl_pairs(A, i, o);
             Win::pairs(g, i, gv);
             if (!INIT) {
                 Win::pairs(d, i, dv);
@@ -203,7 +216,7 @@ struct TriPrepF {
 #pragma unroll
             for (int k = 0; k < B; ++k)
 #pragma unroll
-                for (int t = L - k - 1; t <= H; ++t) o[k][t] = cpl(k + 1, r0 + t);
+                for (int t = L - k - 1; t <= H; ++t) o[k][t] = Win::cpl(A, k + 1, r0 + t);
 #pragma unroll
             for (int t = L; t <= H; ++t) gv[t] = at(g, r0 + t);
             if (!INIT) {
@@ -230,13 +243,7 @@ struct TriPrepF {
         }
         double qv[2];
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int t = 2 * B + h;
-            double s = fma(o[0][t], rr[t + 1], o[0][t - 1] * rr[t - 1]);
-#pragma unroll
-            for (int k = 2; k <= B; ++k) s = fma(o[k - 1][t], rr[t + k], fma(o[k - 1][t - k], rr[t - k], s));
-            qv[h] = s;
-        }
+        for (int h = 0; h < 2; ++h) qv[h] = Win::neighbours(o, rr, 2 * B + h);
         if (v1) {
             st2(q + i, make_double2(qv[0], qv[1]));
             if (!INIT) st2(ad + i, make_double2(adv[2 * B], adv[2 * B + 1]));
@@ -271,24 +278,14 @@ struct TriPrepSF {
     using Win = BandWin<B>;
     static constexpr int W = Win::W, L = Win::L, H = Win::H;
     __device__ __forceinline__ bool skip() const { return ld_stat(istat + I_STATUS) != ST_RUNNING; }
-    __device__ __forceinline__ double at(const double* v, int64_t r) const {      // (clamped index + select, as TriPrepF)
-        const int64_t rc = r < 0 ? 0 : (r >= A.n ? A.n - 1 : r);
-        const double x = v[rc];
-        return (r == rc) ? x : 0.0;
-    }
-    __device__ __forceinline__ double cpl(int k, int64_t r) const {
-        const int64_t rc = r < 0 ? 0 : (r >= A.n ? A.n - 1 : r);
-        const double x = A.col(k)[rc];
-        return (r >= 0 && r + k < A.n) ? x : 0.0;
-    }
+    __device__ __forceinline__ double at(const double* v, int64_t r) const { return Win::at(v, A.n, r); }
     __device__ __forceinline__ void apply(int64_t i, bool v0, bool v1, double*) const {
         if (!v0) return;
         const double alpha = INIT ? 0.0 : ld_scal(scal + S_ALPHA);
         const int64_t r0 = i - 2 * B;
         double o[B][W], dxv[W], axv[W], gx[W], gy[W], dy[W], ay[W], Dxv[W], Dyv[W], adv[W], ux[W];
         if (i >= 2 * B && i + 2 * B + 2 < A.n) {                                 // interior: aligned pair loads (hs is even)
-#pragma unroll
-            for (int k = 0; k < B; ++k) Win::pairs(A.col(k + 1), i, o[k]);
+            Win::cpl_pairs(A, i, o);
             Win::pairs(g, i, gx); Win::pairs(g + hs, i, gy); Win::pairs(Dx, i, Dxv); Win::pairs(Dy, i, Dyv);
             if (!INIT) {
                 Win::pairs(d, i, dxv);
@@ -306,7 +303,7 @@ struct TriPrepSF {
 #pragma unroll
             for (int k = 0; k < B; ++k)
 #pragma unroll
-                for (int t = L - k - 1; t <= H; ++t) o[k][t] = cpl(k + 1, r0 + t);
+                for (int t = L - k - 1; t <= H; ++t) o[k][t] = Win::cpl(A, k + 1, r0 + t);
 #pragma unroll
             for (int t = L; t <= H; ++t) {
                 const int64_t r = r0 + t;
@@ -341,13 +338,7 @@ struct TriPrepSF {
         }
         double qv[2];
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int t = 2 * B + h;
-            double s = fma(o[0][t], ux[t + 1], o[0][t - 1] * ux[t - 1]);
-#pragma unroll
-            for (int k = 2; k <= B; ++k) s = fma(o[k - 1][t], ux[t + k], fma(o[k - 1][t - k], ux[t - k], s));
-            qv[h] = s;
-        }
+        for (int h = 0; h < 2; ++h) qv[h] = Win::neighbours(o, ux, 2 * B + h);
         if (v1) {
             st2(q + i, make_double2(qv[0], qv[1]));
             if (!INIT) st2(ad + i, make_double2(adv[2 * B], adv[2 * B + 1]));
@@ -842,7 +833,7 @@ struct PcgFuseLR {
 // pass and rr = g + alpha A d made of STORED vectors:
 //   U'(A gp)  = U'(A rr) - (U'A U) t          -- the second product carries (A rr)_i = ax_i rr_i + q_i, with q (the neighbours' part) and A d
 //                                                prepared by a vector kernel (TriPrepF), the m x m matrix M = U'A U formed once per solve
-//                                                (tri_reduced_operator below);
+//                                                (reduced_operator below);
 //   gp'A gp   = rr'A rr - 2 t'(U'A rr) + t'M t  (post-op; the three terms are of the size of |A| |rr|^2, and rr differs from gp by what ONE
 //                                                step alpha A d left in the range of U: no cancellation beyond a digit or two);
 //   gp'A d, d'A d: row-local with A d stored.
@@ -853,7 +844,7 @@ struct PcgFuseLR {
 // Per row, ww = Dx rx + Dy ry (the diagonal block of Q'rr) and  u = rr - (Dx, Dy) ww  are row-local, and gp = u - (sx, sy) (Z t) as in PcgFuseE.
 // With Q_Z = [sx.*Z; sy.*Z] the split above holds with u in the place of rr:
 //   Q_Z'(A gp) = Z'(sx.*(ax.*ux + q) + sy.*ay.*uy) - M t,   q_i = off_{i-1} ux_{i-1} + off_i ux_{i+1}  (TriPrepSF),
-//                M = Q_Z'A Q_Z = Z' At Z,  At tridiagonal: At_ii = sx_i^2 ax_i + sy_i^2 ay_i,  At_{i,i+1} = sx_i off_i sx_{i+1}  (tri_stack_weights_kernel);
+//                M = Q_Z'A Q_Z = Z' At Z,  At tridiagonal: At_ii = sx_i^2 ax_i + sy_i^2 ay_i,  At_{i,i+1} = sx_i off_i sx_{i+1}  (diags_stack_weights_kernel);
 //   gp'A gp    = u'A u - 2 t'(Q_Z'A u) + t'M t,   u'A u = sum ux (ax ux + q) + ay uy^2   (PcgPostF's triM path unchanged);
 //   rr'gp, gp'gp, gp'A d, d'A d: row-local, with (A d)_x = (T d)_x stored by TriPrepSF and (A d)_y = ay dy formed here.
 // The record is PcgFuseE<true, .>'s plus A d and q: twelve doubles, 8 n m + 112 n bytes per pass next to TriPrepSF's 88 n.
@@ -1377,7 +1368,8 @@ int lfpsqp_factored_basis_supported(const lfpsqp_ctx* ctx, const lfpsqp_mat* A, 
     return 0;
 }
 
-// ---- lfpsqp_projcg_tridiag / lfpsqp_projcg_band: the reduced operator M = Z'A Z of a banded A, once per solve ---------------------------------
+// ---- lfpsqp_projcg_tridiag / _band / _diags: the reduced operator M = Z'A Z of a coupled A, once per solve --------------------------------------
+// (written for a band, column k at distance k; a grid stencil has its run-time distance s_k in that place)
 // With s_k[i] = sign(off_k[i]) and R_{k,i} = Z_i + s_k[i] Z_{i+k} (rows of Z):
 //     off_k[i] (Z_i'Z_{i+k} + Z_{i+k}'Z_i) = |off_k[i]| (R_{k,i}'R_{k,i} - Z_i'Z_i - Z_{i+k}'Z_{i+k}),  so
 //     Z'A Z = sum_{k=1..B} R_k' diag(|off_k|) R_k + Z' diag(c) Z,    c_i = a0 + dg_i - sum_k (|off_k[i]| + |off_k[i-k]|),
@@ -1386,52 +1378,7 @@ int lfpsqp_factored_basis_supported(const lfpsqp_ctx* ctx, const lfpsqp_mat* A, 
 // (for a discrete Laplacian, off = -1, they are the whole of M: no cancellation); c is non-negative for a diagonally dominant A, otherwise its
 // negative part costs one more pass (the normal case for second differences, interior stencil kappa [1, -4, 6, -4, 1]).  The passes are summed
 // in the order k = 1 .. B, + cpos, - cneg.
-template <int B>
-__global__ __launch_bounds__(256) void tri_weights_kernel(BandD<B> A, double* __restrict__ wabs /* B columns, npad apart */,
-                                                          double* __restrict__ sgn /* B columns */, double* __restrict__ cpos, double* __restrict__ cneg,
-                                                          int64_t npad, double* __restrict__ anyneg) {
-    bool neg = false;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < npad; i += (int64_t)gridDim.x * 256) {
-        double cp = 0.0, cn = 0.0;
-        double c = (i < A.n) ? A.a0 + (A.dg ? A.dg[i] : 0.0) : 0.0;
-#pragma unroll
-        for (int k = 1; k <= B; ++k) {
-            double wa = 0.0, sg = 1.0;
-            if (i < A.n) {
-                const double o = (i + k < A.n) ? A.col(k)[i] : 0.0;
-                wa = fabs(o);
-                sg = (o < 0.0) ? -1.0 : 1.0;
-                const double wm = (i >= k) ? fabs(A.col(k)[i - k]) : 0.0;
-                c = c - wa - wm;
-            }
-            wabs[(k - 1) * npad + i] = wa; sgn[(k - 1) * npad + i] = sg;
-        }
-        if (i < A.n) {
-            if (c >= 0.0) cp = c;
-            else { cn = -c; neg = true; }
-            if (c != c) cp = c;                               // (NaN data: let the Gram pass report it)
-        }
-        cpos[i] = cp; cneg[i] = cn;
-    }
-    if (neg) *anyneg = 1.0;
-}
-// stacked basis: the reduced operator Q_Z'A Q_Z = Z' At Z of the banded At = S_x T S_x + S_y diag(ay) S_y (PcgFuseTri<true, .>) -- the same Gram
-// passes as above, over At instead of A:  At_ii = sx_i^2 ax_i + sy_i^2 ay_i,  At_{i,i+k} = sx_i off_k[i] sx_{i+k}
-template <int B>
-__global__ __launch_bounds__(256) void tri_stack_weights_kernel(BandD<B> A, int64_t hs, const double* __restrict__ sx, const double* __restrict__ sy,
-                                                                double* __restrict__ adg, double* __restrict__ aoff /* B columns, npad apart */, int64_t npad) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < npad; i += (int64_t)gridDim.x * 256) {
-        double dv = 0.0;
-        if (i < A.n) {
-            const double ax = A.a0 + (A.dg ? A.dg[i] : 0.0), ay = A.a0 + (A.dg ? A.dg[hs + i] : 0.0);
-            dv = fma(sx[i] * sx[i], ax, sy[i] * sy[i] * ay);
-        }
-        adg[i] = dv;
-#pragma unroll
-        for (int k = 1; k <= B; ++k) aoff[(k - 1) * npad + i] = (i + k < A.n) ? sx[i] * A.col(k)[i] * sx[i + k] : 0.0;
-    }
-}
-// the same two kernels for off-diagonals at run-time distances (DiagsD, lfpsqp_projcg_diags)
+// One kernel pair for the whole family: a band of width B is the descriptor with K = B and s = {1 .. B} (BandD::col(k) = DiagsD::col(k - 1)).
 __global__ __launch_bounds__(256) void diags_weights_kernel(DiagsD A, double* __restrict__ wabs /* K columns, npad apart */, double* __restrict__ sgn,
                                                             double* __restrict__ cpos, double* __restrict__ cneg, int64_t npad, double* __restrict__ anyneg) {
     bool neg = false;
@@ -1458,6 +1405,8 @@ __global__ __launch_bounds__(256) void diags_weights_kernel(DiagsD A, double* __
     }
     if (neg) *anyneg = 1.0;
 }
+// stacked basis: the reduced operator Q_Z'A Q_Z = Z' At Z of At = S_x T S_x + S_y diag(ay) S_y (PcgFuseTri<true, .>) -- the same Gram passes as
+// above, over At instead of A:  At_ii = sx_i^2 ax_i + sy_i^2 ay_i,  At_{i,i+s_k} = sx_i off_k[i] sx_{i+s_k}
 __global__ __launch_bounds__(256) void diags_stack_weights_kernel(DiagsD A, int64_t hs, const double* __restrict__ sx, const double* __restrict__ sy,
                                                                   double* __restrict__ adg, double* __restrict__ aoff /* K columns, npad apart */, int64_t npad) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < npad; i += (int64_t)gridDim.x * 256) {
@@ -1545,28 +1494,9 @@ static int reduced_from_weights(lfpsqp_ctx* ctx, const lfpsqp_mat* Z, int mc, in
     return 0;
 }
 // Mh (m x m, column-major, host) = U'A U for U = Z[:, :mc] (W == nullptr, m == mc) or U = Z[:, :mc] W (W: mc x m, host); sk: a stacked basis,
-// U = [sx; sy] .* (that), and A over the x half (A.n = N rows, dg stacked)
-template <int B>
-static int tri_reduced_operator(lfpsqp_ctx* ctx, const lfpsqp_mat* Z, int mc, const BandD<B>& A0, const double* W, int m, std::vector<double>& Mh,
-                                const StackD* sk = nullptr) {
-    const int64_t n = A0.n;
-    TriWeights w;
-    LF_TRY(tri_weights_alloc(ctx, n, B, sk != nullptr, w));
-    BandD<B> A = A0;
-    if (sk) {
-        hipLaunchKernelGGL(tri_stack_weights_kernel<B>, dim3(w.nblk), dim3(256), 0, ctx->stream, A0, sk->hs, sk->sx, sk->sy, w.adg, w.aoff, w.npad);
-        LF_LAUNCH_CHECK(ctx);
-        A = BandD<B>{0.0, w.adg, w.aoff, w.npad, n, n};
-    }
-    LF_HIP(ctx, hipMemsetAsync(w.anyneg, 0, sizeof(double), ctx->stream));
-    hipLaunchKernelGGL(tri_weights_kernel<B>, dim3(w.nblk), dim3(256), 0, ctx->stream, A, w.wabs, w.sgn, w.cpos, w.cneg, w.npad, w.anyneg);
-    LF_LAUNCH_CHECK(ctx);
-    const int64_t dist[4] = {1, 2, 3, 4};
-    return reduced_from_weights(ctx, Z, mc, n, B, dist, w, W, m, Mh);
-}
-// ... for off-diagonals at run-time distances (A0.n = A0.nc = the rows of Z)
-static int diags_reduced_operator(lfpsqp_ctx* ctx, const lfpsqp_mat* Z, int mc, const DiagsD& A0, const double* W, int m, std::vector<double>& Mh,
-                                  const StackD* sk = nullptr) {
+// U = [sx; sy] .* (that), and A over the x half (A0.n = A0.nc = N, the rows of Z; dg stacked)
+static int reduced_operator(lfpsqp_ctx* ctx, const lfpsqp_mat* Z, int mc, const DiagsD& A0, const double* W, int m, std::vector<double>& Mh,
+                            const StackD* sk = nullptr) {
     const int64_t n = A0.n;
     TriWeights w;
     LF_TRY(tri_weights_alloc(ctx, n, A0.K, sk != nullptr, w));
@@ -1582,18 +1512,27 @@ static int diags_reduced_operator(lfpsqp_ctx* ctx, const lfpsqp_mat* Z, int mc, 
     return reduced_from_weights(ctx, Z, mc, n, A0.K, A0.s, w, W, m, Mh);
 }
 
-// the banded operator of lfpsqp_projcg_tridiag (bw = 1, off a vector) and lfpsqp_projcg_band (off a plain matrix): bw coupling columns of `rows`
-// entries, ld apart
-struct BandOp {
+// A coupled operator as its entry point describes it: K coupling columns of `rows` entries, ld apart, next to the diagonal (a0, dg).
+//   BAND   column k couples rows i and i + k + 1, K = the bandwidth (1 .. 4) is a compile-time parameter of the kernels (BandD<K>, register
+//          windows): lfpsqp_projcg_tridiag (K = 1, off a vector), lfpsqp_projcg_band (off a plain matrix) and their _mul;
+//   DIAGS  column k couples rows i and i + dist[k], run-time distances (DiagsD, gathers): lfpsqp_projcg_diags, lfpsqp_diags_mul.
+struct CoupledOp {
+    enum Kind { BAND, DIAGS } kind;
+    const char* who;          // the entry point, for messages
     double a0;
     const lfpsqp_vec* dg;
     const double* off;
     int64_t ld, rows;
-    int bw;                   // 0: off-diagonals at the K run-time distances below (lfpsqp_projcg_diags)
-    int K = 0;
-    int64_t dist[4] = {0, 0, 0, 0};
+    int K;
+    int64_t dist[4];          // BAND: {1, 2, 3, 4}
+    const double* dgp() const { return dg ? dg->p : nullptr; }
     // over vectors of n rows, couplings on the first nc
-    DiagsD diags(const double* dgp, int64_t n, int64_t nc) const { return DiagsD{a0, dgp, off, ld, n, nc, K, {dist[0], dist[1], dist[2], dist[3]}}; }
+    DiagsD diags(int64_t n, int64_t nc) const { return DiagsD{a0, dgp(), off, ld, n, nc, K, {dist[0], dist[1], dist[2], dist[3]}}; }
+    template <int B>
+    BandD<B> band(int64_t n, int64_t nc) const { return BandD<B>{a0, dgp(), off, ld, n, nc}; }
+    static CoupledOp banded(const char* who, double a0, const lfpsqp_vec* dg, const double* off, int64_t ld, int64_t rows, int bw) {
+        return CoupledOp{BAND, who, a0, dg, off, ld, rows, bw, {1, 2, 3, 4}};
+    }
 };
 // fn(std::integral_constant<int, B>) for B = bw (1 .. 4)
 template <typename F>
@@ -1606,19 +1545,47 @@ static int with_band(int bw, F&& fn) {
     }
 }
 
-static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const lfpsqp_diag_op* A, lfpsqp_opfun opf, void* ouser,
-                       lfpsqp_vec* Av, const lfpsqp_basis* U, const lfpsqp_vec* b, const lfpsqp_vec* c, double tol, int64_t maxit,
-                       int64_t n_global, int flags, const lfpsqp_projcg_work* work, int64_t* iters, double* nr,
-                       const lfpsqp_lowrank_op* LRop = nullptr, const BandOp* TRop = nullptr) {
-    const lfpsqp_diag_op no_diag = {0.0, nullptr};
-    lfpsqp_diag_op lr_diag = {0.0, nullptr};
-    if (LRop) { lr_diag.a0 = LRop->a0; lr_diag.dg = LRop->dg; A = &lr_diag; }
-    if (TRop) { lr_diag.a0 = TRop->a0; lr_diag.dg = TRop->dg; A = &lr_diag; }
-    if (opf) A = &no_diag;
-    LF_ARG(ctx, ctx && x && A && U && b && work && iters && nr);
-    // (a tridiagonal operator may start from the state lfpsqp_tangent_step left -- LFPSQP_PROJCG_START_GIVEN: r0 and U'r0 do not involve A -- but not
-    // from its folded initial projection, whose sums were formed with the diagonal alone)
-    LF_ARG(ctx, !(opf || TRop) || (Av && Av->n == b->n && !(flags & (LFPSQP_PROJCG_RESUME | (TRop ? 0 : LFPSQP_PROJCG_START_GIVEN) | LFPSQP_PROJCG_START_PROJECTED))));
+// out = A v over vectors of n rows, couplings on the first nc
+static int coupled_mul(lfpsqp_ctx* ctx, const CoupledOp& A, int64_t n, int64_t nc, const double* v, double* out) {
+    if (A.kind == CoupledOp::DIAGS) return run_vec<DiagsMulF, 0, NoPost>(ctx, n, DiagsMulF{A.diags(n, nc), v, out, nullptr}, 0u, nullptr, NoPost());
+    return with_band(A.K, [&](auto Bc) -> int {
+        constexpr int B = decltype(Bc)::value;
+        return run_vec<TriMulF<B>, 0, NoPost>(ctx, n, TriMulF<B>{A.template band<B>(n, nc), v, out, nullptr}, 0u, nullptr, NoPost());
+    });
+}
+// fn(std::bool_constant<stacked>, std::bool_constant<init>)
+template <typename F>
+static int with_stacked_init(bool stacked, bool init, F&& fn) {
+    if (stacked) return init ? fn(std::true_type{}, std::true_type{}) : fn(std::true_type{}, std::false_type{});
+    return init ? fn(std::false_type{}, std::true_type{}) : fn(std::false_type{}, std::false_type{});
+}
+
+// The operator of a solve as the entry points hand it to projcg_impl: exactly one of four kinds.  Every kind but the callback has a
+// device-resident diagonal part `diag`; the callback and the coupled kind bring the work vector Av their products A v land in.
+struct PcgOperator {
+    enum Kind { DIAGONAL, CALLBACK, LOWRANK, COUPLED } kind;
+    lfpsqp_diag_op diag;
+    lfpsqp_opfun fn = nullptr;               // CALLBACK
+    void* user = nullptr;
+    const lfpsqp_lowrank_op* lr = nullptr;   // LOWRANK (k >= 1 columns)
+    const CoupledOp* cp = nullptr;           // COUPLED
+    lfpsqp_vec* Av = nullptr;                // CALLBACK, COUPLED
+};
+
+static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const PcgOperator& op, const lfpsqp_basis* U, const lfpsqp_vec* b,
+                       const lfpsqp_vec* c, double tol, int64_t maxit, int64_t n_global, int flags, const lfpsqp_projcg_work* work,
+                       int64_t* iters, double* nr) {
+    const bool callback = op.kind == PcgOperator::CALLBACK;
+    const lfpsqp_lowrank_op* LRop = op.kind == PcgOperator::LOWRANK ? op.lr : nullptr;
+    const CoupledOp* cop = op.kind == PcgOperator::COUPLED ? op.cp : nullptr;
+    const lfpsqp_diag_op* A = &op.diag;
+    lfpsqp_vec* Av = op.Av;
+    LF_ARG(ctx, ctx && x && U && b && work && iters && nr);
+    if (callback || cop) {
+        // (a coupled operator may start from the state lfpsqp_tangent_step left -- LFPSQP_PROJCG_START_GIVEN: r0 and U'r0 do not involve A -- but not
+        // from its folded initial projection, whose sums were formed with the diagonal alone)
+        LF_ARG(ctx, Av && Av->n == b->n && !(flags & (LFPSQP_PROJCG_RESUME | (cop ? 0 : LFPSQP_PROJCG_START_GIVEN) | LFPSQP_PROJCG_START_PROJECTED)));
+    }
     LF_ARG(ctx, !((flags & LFPSQP_PROJCG_RESUME) && (flags & (LFPSQP_PROJCG_START_GIVEN | LFPSQP_PROJCG_START_PROJECTED))));
     LF_ARG(ctx, !((flags & LFPSQP_PROJCG_START_GIVEN) && (flags & LFPSQP_PROJCG_START_PROJECTED)));
     LF_ARG(ctx, work->g && work->d && work->rp && work->Utr);
@@ -1697,7 +1664,7 @@ static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const
     };
 
     // fused iteration (one pass over U)?  Needs a tile shape for m columns and 32-bit lane offsets
-    const bool fused = !SA && !opf && m > 0 && onepass_cw(ctx, mc, Z->ld, N) != 0;
+    const bool fused = !SA && !callback && m > 0 && onepass_cw(ctx, mc, Z->ld, N) != 0;
     if (DF && !fused)
         return set_err(ctx, LFPSQP_ERR_UNSUPPORTED, "basis in factored form (Z == NULL) needs the fused iteration: diagonal operator, 4 .. 1024 generator "
                                                     "columns; materialise Z = A W for this shape");
@@ -1711,24 +1678,18 @@ static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const
         if (!fused || stacked || (flags & (LFPSQP_PROJCG_RESUME | LFPSQP_PROJCG_START_GIVEN | LFPSQP_PROJCG_START_PROJECTED)))
             return set_err(ctx, LFPSQP_ERR_UNSUPPORTED, "lfpsqp_projcg_lowrank: needs the one-pass iteration over a plain dense basis (4 .. 1024 columns), no RESUME / START_GIVEN");
     }
-    // tridiagonal / banded operator (lfpsqp_projcg_tridiag, lfpsqp_projcg_band): fused iteration only; M = U'A U first (its Gram passes use the
-    // scratch areas reserved below).  Over the x half: BandD<B>{a0, dg, off, ld, N, N}; over whole (stacked) vectors (lfpsqp_tridiag_mul's form):
-    // n = nv, nc = N.
+    // coupled operator (lfpsqp_projcg_tridiag, lfpsqp_projcg_band, lfpsqp_projcg_diags): fused iteration only; M = U'A U first (its Gram passes
+    // use the scratch areas reserved below).  Over the x half: cop->diags(N, N) / cop->band<B>(N, N); over whole (stacked) vectors (the form of
+    // lfpsqp_tridiag_mul): n = nv, nc = N.
     std::vector<double> triMh;
-    const double* tri_dg = (TRop && TRop->dg) ? TRop->dg->p : nullptr;
-    if (TRop) {
+    if (cop) {
         // (stacked: dg over both halves, off the x half's couplings -- N rows; the y half is diagonal)
-        LF_ARG(ctx, TRop->off && TRop->rows == N && TRop->bw >= 0 && TRop->bw <= 4 && (!TRop->dg || TRop->dg->n == nv));
+        LF_ARG(ctx, cop->off && cop->rows == N && cop->K >= 1 && cop->K <= 4 && (!cop->dg || cop->dg->n == nv));
         if (!fused || !plain_mat(Z) || ctx->comm_active())
             return set_err(ctx, LFPSQP_ERR_UNSUPPORTED, "%s: needs the one-pass iteration over a dense basis (4 .. 1024 columns, no matrix "
                                                         "view) on a single rank (the couplings would cross the shard boundaries); use lfpsqp_projcg_op",
-                           TRop->bw == 0 ? "lfpsqp_projcg_diags" : (TRop->bw == 1 ? "lfpsqp_projcg_tridiag" : "lfpsqp_projcg_band"));
-        if (TRop->bw == 0) LF_TRY(diags_reduced_operator(ctx, Z, mc, TRop->diags(tri_dg, N, N), DF ? U->W : nullptr, m, triMh, stacked ? &sk : nullptr));
-        else LF_TRY(with_band(TRop->bw, [&](auto Bc) -> int {
-            constexpr int B = decltype(Bc)::value;
-            return tri_reduced_operator<B>(ctx, Z, mc, BandD<B>{TRop->a0, tri_dg, TRop->off, TRop->ld, N, N}, DF ? U->W : nullptr, m, triMh,
-                                           stacked ? &sk : nullptr);
-        }));
+                           cop->who);
+        LF_TRY(reduced_operator(ctx, Z, mc, cop->diags(N, N), DF ? U->W : nullptr, m, triMh, stacked ? &sk : nullptr));
     }
     double* dTriM = nullptr;
     double *lrUtV = nullptr, *lrSig = nullptr, *lrVdraw = nullptr, *lrVdc = nullptr, *lrVtv = nullptr;
@@ -1745,14 +1706,14 @@ static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const
         if (kLR > 0) {
             lrUtV = tail; lrSig = lrUtV + (size_t)m * kLRMax; lrVdraw = lrSig + kLRMax; lrVdc = lrVdraw + kLRMax; lrVtv = lrVdc + kLRMax;
         }
-        if (DF || TRop) {
+        if (DF || cop) {
             const size_t wsz = DF ? (size_t)round_up((int64_t)mc * m, 2) : 0;
-            LF_TRY(ensure_small(ctx, wsz + (TRop ? (size_t)m * m : 0) + 64));
+            LF_TRY(ensure_small(ctx, wsz + (cop ? (size_t)m * m : 0) + 64));
             if (DF) {
                 dWf = ctx->small;
                 LF_HIP(ctx, hipMemcpyAsync(dWf, U->W, sizeof(double) * (size_t)mc * m, hipMemcpyHostToDevice, ctx->stream));
             }
-            if (TRop) {
+            if (cop) {
                 dTriM = ctx->small + wsz;
                 LF_HIP(ctx, hipMemcpyAsync(dTriM, triMh.data(), sizeof(double) * (size_t)m * m, hipMemcpyHostToDevice, ctx->stream));
             }
@@ -1771,11 +1732,11 @@ static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const
     for (int k = 0; k < kRing; ++k) hstat[kRingOff + k] = ST_RUNNING;
     // the user's operator: Av = A * v, queued on the context's stream (or synchronous) by the callback
     auto apply_op = [&](const lfpsqp_vec* v) -> int {
-        const int rc = opf(ouser, v, Av);
+        const int rc = op.fn(op.user, v, Av);
         if (rc != 0) return set_err(ctx, LFPSQP_ERR_ARG, "operator callback returned %d", rc);
         return 0;
     };
-    const AOpV Aop{(opf || TRop) ? Av->p : nullptr};
+    const AOpV Aop{(callback || cop) ? Av->p : nullptr};
     auto residual_with = [&](auto aop, double sgn, double* store, double* t_out) -> int {
         using AOP = decltype(aop);
         const ResidualV<AOP> rv{x->p, b->p, store, aop, sgn};
@@ -1791,16 +1752,11 @@ static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const
             LF_TRY(run_gemv_t(ctx, LRop->V, kLR, N, SpPlainV{x->p}, lrVtv));
             return residual_with(AOpLR{Ad.a0, Ad.dg, LRop->V->p, LRop->V->ld, kLR, lrSig, lrVtv}, sgn, store, t_out);
         }
-        if (TRop) {                                                           // Av = A x by the stencil kernel, then as a stored product
-            if (TRop->bw == 0) LF_TRY((run_vec<DiagsMulF, 0, NoPost>(ctx, nv, DiagsMulF{TRop->diags(tri_dg, nv, N), x->p, Av->p, nullptr}, 0u, nullptr, NoPost())));
-            else LF_TRY(with_band(TRop->bw, [&](auto Bc) -> int {
-                constexpr int B = decltype(Bc)::value;
-                const BandD<B> Am{TRop->a0, tri_dg, TRop->off, TRop->ld, nv, N};
-                return run_vec<TriMulF<B>, 0, NoPost>(ctx, nv, TriMulF<B>{Am, x->p, Av->p, nullptr}, 0u, nullptr, NoPost());
-            }));
+        if (cop) {                                                           // Av = A x by the stencil kernel, then as a stored product
+            LF_TRY(coupled_mul(ctx, *cop, nv, N, x->p, Av->p));
             return residual_with(Aop, sgn, store, t_out);
         }
-        if (!opf) return residual_with(Ad, sgn, store, t_out);
+        if (!callback) return residual_with(Ad, sgn, store, t_out);
         LF_TRY(apply_op(x));                                                  // Av = A x
         return residual_with(Aop, sgn, store, t_out);
     };
@@ -1812,7 +1768,7 @@ static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const
         if (SA) return sp_gemv_t(sv, tmpN, Utr, uA);
         return run_gemv_t(ctx, Z, m, N, sv, Utr, 1);
     };
-    auto launch_k2 = [&]() -> int { return opf ? k2_with(Aop) : k2_with(Ad); };
+    auto launch_k2 = [&]() -> int { return callback ? k2_with(Aop) : k2_with(Ad); };
     auto k3_with = [&](auto aop, int init) -> int {
         using AOP = decltype(aop);
         const PcgProjE<AOP> pe{rp, g, d, istat, init, PcgStepV<AOP>{d, g, aop, scal, istat}};
@@ -1830,7 +1786,7 @@ static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const
         }
         return run_gemv_n<PcgProjE<AOP>, 2, PcgPost3>(ctx, Z, m, N, Utr, pe, scal + S_RPGP, post, init ? -1 : 2);
     };
-    auto launch_k3 = [&](int init) -> int { return opf ? k3_with(Aop, init) : k3_with(Ad, init); };
+    auto launch_k3 = [&](int init) -> int { return callback ? k3_with(Aop, init) : k3_with(Ad, init); };
 
     // The fused kernel reads the residual of a row a tile ahead and stores the projected one a tile later.  On a box in the slow
     // state of FINDINGS.md §6, removing EITHER that load or that store of the same line made the kernel 13 % faster (1.95 -> 1.70 ms),
@@ -1840,63 +1796,58 @@ static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const
     // (or LFPSQP_GPING=1) turns it on (same bits either way).  gcur = the buffer holding the current g.
     const bool kPing = ctx->tune_gping == 1;
     // (the tridiagonal iteration keeps a vector of its own in rp after the initial projection: no alternation there)
-    double* gbuf[2] = {g, (fused && kPing && !TRop) ? rp : g};
+    double* gbuf[2] = {g, (fused && kPing && !cop) ? rp : g};
     int gcur = 0;
+    // What PcgFuseTri needs from the rows' neighbours, by vector kernels before the pass: ad = A d (from dsrc; not INIT) and q = the off-diagonal
+    // part of A rr, rr = src + alpha ad (stacked: of T ux, the x half projected off the diagonal block); N rows each.
+    auto prepare_neighbours = [&](auto STc, auto INc, const double* src, const double* dsrc, double* ad, double* q) -> int {
+        constexpr bool ST = decltype(STc)::value, INIT = decltype(INc)::value;
+        if (cop->kind == CoupledOp::BAND)             // near neighbours: one kernel with a register window
+            return with_band(cop->K, [&](auto Bc) -> int {
+                constexpr int B = decltype(Bc)::value;
+                const BandD<B> Ab = cop->template band<B>(N, N);
+                if constexpr (ST) return run_vec<TriPrepSF<B, INIT>, 0, NoPost>(ctx, N, TriPrepSF<B, INIT>{Ab, hs, sk.Dx, sk.Dy, src, dsrc, ad, q, scal, istat}, 0u, nullptr, NoPost());
+                else return run_vec<TriPrepF<B, INIT>, 0, NoPost>(ctx, N, TriPrepF<B, INIT>{Ab, src, dsrc, ad, q, scal, istat}, 0u, nullptr, NoPost());
+            });
+        // run-time distances: A d stored first, then the gather of the neighbours' rr (stacked: of ux, kept in the set-up's scratch, which is
+        // free once M is on the device)
+        const DiagsD Ab = cop->diags(N, N);
+        if constexpr (ST) {
+            double* ux = ctx->d_tri;
+            LF_TRY((run_vec<DiagsPrepSF<INIT>, 0, NoPost>(ctx, N, DiagsPrepSF<INIT>{Ab, hs, sk.Dx, sk.Dy, src, dsrc, ad, ux, scal, istat}, 0u, nullptr, NoPost())));
+            return run_vec<DiagsGatherF, 0, NoPost>(ctx, N, DiagsGatherF{Ab, ux, nullptr, q, scal, istat}, 0u, nullptr, NoPost());
+        } else {
+            if constexpr (!INIT) LF_TRY((run_vec<DiagsMulF, 0, NoPost>(ctx, N, DiagsMulF{Ab, dsrc, ad, istat}, 0u, nullptr, NoPost())));
+            return run_vec<DiagsGatherF, 0, NoPost>(ctx, N, DiagsGatherF{Ab, src, ad, q, scal, istat}, 0u, nullptr, NoPost());
+        }
+    };
     auto launch_fused = [&](int init) -> int {
         const int slot = init ? -1 : 3;
         const double* gin = gbuf[gcur];
         double* gout = init ? gbuf[0] : gbuf[gcur ^ 1];
         const double* tin = DF ? uDF : Utr;               // coefficients of the first product over the streamed matrix's mc columns
         double* Tout = DF ? Traw : T12;
-        // tridiagonal / banded: the neighbours' contributions first (a vector kernel), into Av while rp still holds the initial residual, into rp
-        // afterwards (stacked: both into the first N entries).  The pass itself does not depend on the bandwidth.
-        if (TRop && TRop->bw == 0) {
-            // off-diagonals at run-time distances: A d stored first, then the gather of the neighbours' rr (stacked: of ux, kept in the set-up's
-            // scratch, which is free once M is on the device); the same four passes
-            const DiagsD Ab = TRop->diags(tri_dg, N, N);
-            double* ux = ctx->d_tri;
-            if (stacked && init) {
-                LF_TRY((run_vec<DiagsPrepSF<true>, 0, NoPost>(ctx, N, DiagsPrepSF<true>{Ab, hs, sk.Dx, sk.Dy, rp, nullptr, nullptr, ux, scal, istat}, 0u, nullptr, NoPost())));
-                LF_TRY((run_vec<DiagsGatherF, 0, NoPost>(ctx, N, DiagsGatherF{Ab, ux, nullptr, Av->p, scal, istat}, 0u, nullptr, NoPost())));
-                LF_TRY((run_onepass<PcgFuseTri<true, true>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseTri<true, true>{rp, gin, gout, d, nullptr, Av->p, Ad, scal, istat, sk}, Tout, slot)));
-            } else if (stacked) {
-                LF_TRY((run_vec<DiagsPrepSF<false>, 0, NoPost>(ctx, N, DiagsPrepSF<false>{Ab, hs, sk.Dx, sk.Dy, gin, d, Av->p, ux, scal, istat}, 0u, nullptr, NoPost())));
-                LF_TRY((run_vec<DiagsGatherF, 0, NoPost>(ctx, N, DiagsGatherF{Ab, ux, nullptr, rp, scal, istat}, 0u, nullptr, NoPost())));
-                LF_TRY((run_onepass<PcgFuseTri<true, false>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseTri<true, false>{rp, gin, gout, d, Av->p, rp, Ad, scal, istat, sk}, Tout, slot)));
-            } else if (init) {
-                LF_TRY((run_vec<DiagsGatherF, 0, NoPost>(ctx, nv, DiagsGatherF{Ab, rp, nullptr, Av->p, scal, istat}, 0u, nullptr, NoPost())));
-                LF_TRY((run_onepass<PcgFuseTri<false, true>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseTri<false, true>{rp, gin, gout, d, nullptr, Av->p, Ad, scal, istat, sk}, Tout, slot)));
-            } else {
-                LF_TRY((run_vec<DiagsMulF, 0, NoPost>(ctx, nv, DiagsMulF{Ab, d, Av->p, istat}, 0u, nullptr, NoPost())));
-                LF_TRY((run_vec<DiagsGatherF, 0, NoPost>(ctx, nv, DiagsGatherF{Ab, gin, Av->p, rp, scal, istat}, 0u, nullptr, NoPost())));
-                LF_TRY((run_onepass<PcgFuseTri<false, false>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseTri<false, false>{rp, gin, gout, d, Av->p, rp, Ad, scal, istat, sk}, Tout, slot)));
-            }
-        } else if (TRop) {
-            LF_TRY(with_band(TRop->bw, [&](auto Bc) -> int {
-                constexpr int B = decltype(Bc)::value;
-                const BandD<B> Ab{TRop->a0, tri_dg, TRop->off, TRop->ld, N, N};
-                if (stacked && init) {
-                    LF_TRY((run_vec<TriPrepSF<B, true>, 0, NoPost>(ctx, N, TriPrepSF<B, true>{Ab, hs, sk.Dx, sk.Dy, rp, nullptr, nullptr, Av->p, scal, istat}, 0u, nullptr, NoPost())));
-                    LF_TRY((run_onepass<PcgFuseTri<true, true>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseTri<true, true>{rp, gin, gout, d, nullptr, Av->p, Ad, scal, istat, sk}, Tout, slot)));
-                } else if (stacked) {
-                    LF_TRY((run_vec<TriPrepSF<B, false>, 0, NoPost>(ctx, N, TriPrepSF<B, false>{Ab, hs, sk.Dx, sk.Dy, gin, d, Av->p, rp, scal, istat}, 0u, nullptr, NoPost())));
-                    LF_TRY((run_onepass<PcgFuseTri<true, false>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseTri<true, false>{rp, gin, gout, d, Av->p, rp, Ad, scal, istat, sk}, Tout, slot)));
-                } else if (init) {
-                    LF_TRY((run_vec<TriPrepF<B, true>, 0, NoPost>(ctx, nv, TriPrepF<B, true>{Ab, rp, nullptr, nullptr, Av->p, scal, istat}, 0u, nullptr, NoPost())));
-                    LF_TRY((run_onepass<PcgFuseTri<false, true>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseTri<false, true>{rp, gin, gout, d, nullptr, Av->p, Ad, scal, istat, sk}, Tout, slot)));
-                } else {
-                    LF_TRY((run_vec<TriPrepF<B, false>, 0, NoPost>(ctx, nv, TriPrepF<B, false>{Ab, gin, d, Av->p, rp, scal, istat}, 0u, nullptr, NoPost())));
-                    LF_TRY((run_onepass<PcgFuseTri<false, false>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseTri<false, false>{rp, gin, gout, d, Av->p, rp, Ad, scal, istat, sk}, Tout, slot)));
-                }
-                return 0;
-            }));
-        }
-        else if (kLR > 0 && init) LF_TRY((run_onepass<PcgFuseLR<true>, 2, 5 + kLRMax>(ctx, Z, mc, mc, N, tin, PcgFuseLR<true>{rp, gin, gout, d, Ad, scal, istat, LRop->V->p, LRop->V->ld, kLR, lrVdc}, Tout, slot)));
-        else if (kLR > 0) LF_TRY((run_onepass<PcgFuseLR<false>, 2, 5 + kLRMax>(ctx, Z, mc, mc, N, tin, PcgFuseLR<false>{rp, gin, gout, d, Ad, scal, istat, LRop->V->p, LRop->V->ld, kLR, lrVdc}, Tout, slot)));
-        else if (stacked && init) LF_TRY((run_onepass<PcgFuseE<true, true>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseE<true, true>{rp, gin, gout, d, Ad, scal, istat, sk}, Tout, slot)));
-        else if (stacked) LF_TRY((run_onepass<PcgFuseE<true, false>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseE<true, false>{rp, gin, gout, d, Ad, scal, istat, sk}, Tout, slot)));
-        else if (init) LF_TRY((run_onepass<PcgFuseE<false, true>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseE<false, true>{rp, gin, gout, d, Ad, scal, istat, sk}, Tout, slot)));
-        else LF_TRY((run_onepass<PcgFuseE<false, false>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseE<false, false>{rp, gin, gout, d, Ad, scal, istat, sk}, Tout, slot)));
+        auto fuse_lr = [&](auto INc) -> int {             // (never stacked: refused above)
+            constexpr bool INIT = decltype(INc)::value;
+            return run_onepass<PcgFuseLR<INIT>, 2, 5 + kLRMax>(ctx, Z, mc, mc, N, tin, PcgFuseLR<INIT>{rp, gin, gout, d, Ad, scal, istat, LRop->V->p, LRop->V->ld, kLR, lrVdc}, Tout, slot);
+        };
+        // (one dispatch per functor family, in this order: the kernels are instantiated in the order the families are named here)
+        if (cop) LF_TRY(with_stacked_init(stacked, init != 0, [&](auto STc, auto INc) -> int {
+            constexpr bool ST = decltype(STc)::value, INIT = decltype(INc)::value;
+            // the neighbours' contributions first (vector kernels): q into Av while rp still holds the initial residual, into rp afterwards,
+            // A d into Av (stacked: both into the first N entries).  The pass itself does not depend on the kind of the couplings.
+            const double* src = INIT ? rp : gin;
+            const double* dsrc = INIT ? nullptr : d;
+            double* ad = INIT ? nullptr : Av->p;
+            double* q = INIT ? Av->p : rp;
+            LF_TRY(prepare_neighbours(STc, INc, src, dsrc, ad, q));
+            return run_onepass<PcgFuseTri<ST, INIT>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseTri<ST, INIT>{rp, gin, gout, d, ad, q, Ad, scal, istat, sk}, Tout, slot);
+        }));
+        else if (kLR > 0) LF_TRY(init ? fuse_lr(std::true_type{}) : fuse_lr(std::false_type{}));
+        else LF_TRY(with_stacked_init(stacked, init != 0, [&](auto STc, auto INc) -> int {
+            constexpr bool ST = decltype(STc)::value, INIT = decltype(INc)::value;
+            return run_onepass<PcgFuseE<ST, INIT>, 2, 5>(ctx, Z, mc, mc, N, tin, PcgFuseE<ST, INIT>{rp, gin, gout, d, Ad, scal, istat, sk}, Tout, slot);
+        }));
         if (!init) gcur ^= 1;
         PcgPostF pf{T12, t3, Utr, scal, istat, m, init, hm, dWf, Traw, T12, uDF, DF ? mc : 0};
         if (kLR > 0) { pf.k = kLR; pf.UtV = lrUtV; pf.sigma = lrSig; pf.vdraw = lrVdraw; pf.vdc = lrVdc; }
@@ -1982,7 +1933,7 @@ static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const
             // one global reduction per iteration: the post-op of F has already done the exits and alpha of this iteration
             if (it > 0 || resume) LF_TRY((run_vec<PcgDirG, 0, NoPost>(ctx, nv, PcgDirG{d, gbuf[gcur], x->p, scal, istat, 0}, 0u, nullptr, NoPost(), 0)));
             LF_TRY(launch_fused(0));
-        } else if (opf) {
+        } else if (callback) {
             // generic operator: the direction update, then the user's product A d, then d'(A d); the two passes over U read A d
             if (it > 0) LF_TRY((run_vec<PcgDirX, 0, NoPost>(ctx, nv, PcgDirX{d, g, x->p, scal, istat}, 0u, nullptr, NoPost(), 0)));
             LF_TRY(apply_op(work->d));
@@ -2020,7 +1971,7 @@ static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const
     // flow the exits of an iteration start are taken before its K1, so they leave it pending too)
     if ((status == ST_CONVERGED || status == ST_MAXIT || (fused && status == ST_RG_BREAK && *iters > 1)) && *iters > it_base)
         LF_TRY((run_vec<FlushXF, 0, NoPost>(ctx, nv, FlushXF{x->p, d, scal}, 0u, nullptr, NoPost())));
-    if (fused && status == ST_MAXIT && *iters > 0 && kLR == 0 && !TRop)
+    if (fused && status == ST_MAXIT && *iters > 0 && kLR == 0 && !cop)
         ctx->pcg_resume = lfpsqp_ctx::ProjcgResume{true, x->p, g, d, Z->p, m, nv, *iters, gcur == 1, Ad.dg, b->p, Ad.a0, n_global, ctx->launch_epoch};
     if (status == ST_NEGCURV) {   // :77-82
         if (fused && *iters > 1)  // d+ = beta d - g of the iteration that found the negative curvature was not formed yet
@@ -2052,7 +2003,6 @@ int lfpsqp::placement_probe(lfpsqp_ctx* ctx, const lfpsqp_mat* M, int ncols, dou
     hipLaunchKernelGGL((post_kernel<InitState>), dim3(1), dim3(1), 0, ctx->stream, ctx->scal, InitState{ctx->scal, ctx->istat, 0.0, (int64_t)1 << 40});
     LF_LAUNCH_CHECK(ctx);
     const StackD sk{0, nullptr, nullptr, nullptr, nullptr};
-    const PcgFuseE<false, false> f{g, g, g, d, AOpD{0.0, a}, ctx->scal, ctx->istat, sk};
     // The trial is LOCAL: no collective inside it.  How many candidates a rank tries depends on its own shard size and free memory, so a
     // trial that all-reduced its (meaningless) sums would leave the ranks with different numbers of collectives in flight.
     const Comm::Kind saved = ctx->comm.kind;
@@ -2060,7 +2010,12 @@ int lfpsqp::placement_probe(lfpsqp_ctx* ctx, const lfpsqp_mat* M, int ncols, dou
     int rc = 0;
     for (int k = 0; k < reps + 1 && rc == 0; ++k) {
         if (k == 1) rc = hipEventRecord(ctx->ev_t0, ctx->stream) == hipSuccess ? 0 : LFPSQP_ERR_HIP;
-        if (rc == 0) rc = run_onepass<PcgFuseE<false, false>, 2, 5>(ctx, M, ncols, ncols, M->n, Utr, f, T12, -1);
+        // (through the solve's own dispatch, not PcgFuseE<false, false> by name: named here, the probe would be the first to instantiate the
+        // headline kernel, before its siblings, and the compiler schedules one instruction of its prologue differently then)
+        if (rc == 0) rc = with_stacked_init(false, false, [&](auto STc, auto INc) -> int {
+            constexpr bool ST = decltype(STc)::value, INIT = decltype(INc)::value;
+            return run_onepass<PcgFuseE<ST, INIT>, 2, 5>(ctx, M, ncols, ncols, M->n, Utr, PcgFuseE<ST, INIT>{g, g, g, d, AOpD{0.0, a}, ctx->scal, ctx->istat, sk}, T12, -1);
+        });
     }
     ctx->comm.kind = saved;
     LF_TRY(rc);
@@ -2077,7 +2032,7 @@ extern "C" int lfpsqp_projcg(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda,
                              const lfpsqp_projcg_work* work, int64_t* iters, double* nr) {
     LF_RANGE("lfpsqp_projcg");
     LF_ARG(ctx, ctx && A);
-    return projcg_impl(ctx, x, lambda, A, nullptr, nullptr, nullptr, U, b, c, tol, maxit, n_global, flags, work, iters, nr);
+    return projcg_impl(ctx, x, lambda, PcgOperator{PcgOperator::DIAGONAL, *A}, U, b, c, tol, maxit, n_global, flags, work, iters, nr);
 }
 
 extern "C" int lfpsqp_projcg_lowrank(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const lfpsqp_lowrank_op* A, const lfpsqp_basis* U,
@@ -2085,11 +2040,28 @@ extern "C" int lfpsqp_projcg_lowrank(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec*
                                      const lfpsqp_projcg_work* work, int64_t* iters, double* nr) {
     LF_RANGE("lfpsqp_projcg_lowrank");
     LF_ARG(ctx, ctx && A);
-    if (A->k == 0) {
-        const lfpsqp_diag_op dop{A->a0, A->dg};
-        return projcg_impl(ctx, x, lambda, &dop, nullptr, nullptr, nullptr, U, b, c, tol, maxit, n_global, flags, work, iters, nr);
-    }
-    return projcg_impl(ctx, x, lambda, nullptr, nullptr, nullptr, nullptr, U, b, c, tol, maxit, n_global, flags, work, iters, nr, A);
+    PcgOperator op{A->k == 0 ? PcgOperator::DIAGONAL : PcgOperator::LOWRANK, lfpsqp_diag_op{A->a0, A->dg}};
+    op.lr = A;
+    return projcg_impl(ctx, x, lambda, op, U, b, c, tol, maxit, n_global, flags, work, iters, nr);
+}
+
+static int projcg_coupled(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const CoupledOp& A, lfpsqp_vec* Av, const lfpsqp_basis* U,
+                          const lfpsqp_vec* b, const lfpsqp_vec* c, double tol, int64_t maxit, int64_t n_global, int flags,
+                          const lfpsqp_projcg_work* work, int64_t* iters, double* nr) {
+    PcgOperator op{PcgOperator::COUPLED, lfpsqp_diag_op{A.a0, A.dg}};
+    op.cp = &A;
+    op.Av = Av;
+    return projcg_impl(ctx, x, lambda, op, U, b, c, tol, maxit, n_global, flags, work, iters, nr);
+}
+
+// out = A v for a coupled operator: off of n rows, or of N rows for a stacked pair (v->n = half stride + N: the couplings act on the x half,
+// the rest is diagonal)
+static int coupled_mul_entry(lfpsqp_ctx* ctx, const CoupledOp& A, const lfpsqp_vec* v, lfpsqp_vec* out) {
+    LF_ARG(ctx, v && out && v != out && v->p != out->p && out->n == v->n && (!A.dg || A.dg->n == v->n));
+    LF_ARG(ctx, A.rows == v->n || (A.rows > 0 && v->n == lfpsqp_half_stride(A.rows) + A.rows));
+    if (ctx->comm_active())        // (a rank sees its own rows only: the couplings across the shard boundaries would silently drop out)
+        return set_err(ctx, LFPSQP_ERR_UNSUPPORTED, "%s: one rank only (no halo exchange between row shards)", A.who);
+    return coupled_mul(ctx, A, v->n, A.rows, v->p, out->p);
 }
 
 extern "C" int lfpsqp_projcg_tridiag(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const lfpsqp_tridiag_op* A, lfpsqp_vec* Av, const lfpsqp_basis* U,
@@ -2097,8 +2069,13 @@ extern "C" int lfpsqp_projcg_tridiag(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec*
                                      const lfpsqp_projcg_work* work, int64_t* iters, double* nr) {
     LF_RANGE("lfpsqp_projcg_tridiag");
     LF_ARG(ctx, ctx && A && Av && A->off);
-    const BandOp bop{A->a0, A->dg, A->off->p, A->off->n, A->off->n, 1};
-    return projcg_impl(ctx, x, lambda, nullptr, nullptr, nullptr, Av, U, b, c, tol, maxit, n_global, flags, work, iters, nr, nullptr, &bop);
+    return projcg_coupled(ctx, x, lambda, CoupledOp::banded("lfpsqp_projcg_tridiag", A->a0, A->dg, A->off->p, A->off->n, A->off->n, 1), Av, U, b, c,
+                          tol, maxit, n_global, flags, work, iters, nr);
+}
+
+extern "C" int lfpsqp_tridiag_mul(lfpsqp_ctx* ctx, const lfpsqp_tridiag_op* A, const lfpsqp_vec* v, lfpsqp_vec* out) {
+    LF_ARG(ctx, ctx && A && A->off);
+    return coupled_mul_entry(ctx, CoupledOp::banded("lfpsqp_tridiag_mul", A->a0, A->dg, A->off->p, A->off->n, A->off->n, 1), v, out);
 }
 
 extern "C" int lfpsqp_projcg_band(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, double a0, const lfpsqp_vec* dg, const lfpsqp_mat* off, int64_t bw,
@@ -2106,43 +2083,23 @@ extern "C" int lfpsqp_projcg_band(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* la
                                   int64_t n_global, int flags, const lfpsqp_projcg_work* work, int64_t* iters, double* nr) {
     LF_RANGE("lfpsqp_projcg_band");
     LF_ARG(ctx, ctx && Av && off && plain_mat(off) && bw >= 1 && bw <= 4 && off->m >= bw);
-    const BandOp bop{a0, dg, off->p, off->ld, off->n, (int)bw};
-    return projcg_impl(ctx, x, lambda, nullptr, nullptr, nullptr, Av, U, b, c, tol, maxit, n_global, flags, work, iters, nr, nullptr, &bop);
-}
-
-// out = A v for the banded operator: off of n rows, or of N rows for a stacked pair (v->n = half stride + N: the couplings act on the x half,
-// the rest is diagonal)
-static int band_mul(lfpsqp_ctx* ctx, const char* who, double a0, const lfpsqp_vec* dg, const double* off, int64_t ld, int64_t rows, int bw,
-                    const lfpsqp_vec* v, lfpsqp_vec* out) {
-    LF_ARG(ctx, v && out && v != out && v->p != out->p && out->n == v->n && (!dg || dg->n == v->n));
-    LF_ARG(ctx, rows == v->n || (rows > 0 && v->n == lfpsqp_half_stride(rows) + rows));
-    if (ctx->comm_active())        // (a rank sees its own rows only: the couplings across the shard boundaries would silently drop out)
-        return set_err(ctx, LFPSQP_ERR_UNSUPPORTED, "%s: one rank only (no halo exchange between row shards)", who);
-    return with_band(bw, [&](auto Bc) -> int {
-        constexpr int B = decltype(Bc)::value;
-        const BandD<B> A{a0, dg ? dg->p : nullptr, off, ld, v->n, rows};
-        return run_vec<TriMulF<B>, 0, NoPost>(ctx, v->n, TriMulF<B>{A, v->p, out->p, nullptr}, 0u, nullptr, NoPost());
-    });
-}
-
-extern "C" int lfpsqp_tridiag_mul(lfpsqp_ctx* ctx, const lfpsqp_tridiag_op* A, const lfpsqp_vec* v, lfpsqp_vec* out) {
-    LF_ARG(ctx, ctx && A && A->off);
-    return band_mul(ctx, "lfpsqp_tridiag_mul", A->a0, A->dg, A->off->p, A->off->n, A->off->n, 1, v, out);
+    return projcg_coupled(ctx, x, lambda, CoupledOp::banded("lfpsqp_projcg_band", a0, dg, off->p, off->ld, off->n, (int)bw), Av, U, b, c, tol, maxit,
+                          n_global, flags, work, iters, nr);
 }
 
 extern "C" int lfpsqp_band_mul(lfpsqp_ctx* ctx, double a0, const lfpsqp_vec* dg, const lfpsqp_mat* off, int64_t bw, const lfpsqp_vec* v, lfpsqp_vec* out) {
     LF_ARG(ctx, ctx && off && plain_mat(off) && bw >= 1 && bw <= 4 && off->m >= bw);
-    return band_mul(ctx, "lfpsqp_band_mul", a0, dg, off->p, off->ld, off->n, (int)bw, v, out);
+    return coupled_mul_entry(ctx, CoupledOp::banded("lfpsqp_band_mul", a0, dg, off->p, off->ld, off->n, (int)bw), v, out);
 }
 
 // the off-diagonals of lfpsqp_projcg_diags / lfpsqp_diags_mul: K (1 .. 4) columns of a plain matrix, strictly increasing distances in 1 .. rows - 1
-static int diags_op(lfpsqp_ctx* ctx, double a0, const lfpsqp_vec* dg, const lfpsqp_mat* off, int64_t K, const int64_t* dist, BandOp& bop) {
+static int diags_op(lfpsqp_ctx* ctx, const char* who, double a0, const lfpsqp_vec* dg, const lfpsqp_mat* off, int64_t K, const int64_t* dist,
+                    CoupledOp& A) {
     LF_ARG(ctx, off && plain_mat(off) && dist && K >= 1 && K <= 4 && off->m >= K);
-    bop = BandOp{a0, dg, off->p, off->ld, off->n, 0};
-    bop.K = (int)K;
+    A = CoupledOp{CoupledOp::DIAGS, who, a0, dg, off->p, off->ld, off->n, (int)K, {0, 0, 0, 0}};
     for (int k = 0; k < K; ++k) {
         LF_ARG(ctx, dist[k] >= 1 && dist[k] < off->n && (k == 0 || dist[k] > dist[k - 1]));
-        bop.dist[k] = dist[k];
+        A.dist[k] = dist[k];
     }
     return 0;
 }
@@ -2152,21 +2109,17 @@ extern "C" int lfpsqp_projcg_diags(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* l
                                    int64_t maxit, int64_t n_global, int flags, const lfpsqp_projcg_work* work, int64_t* iters, double* nr) {
     LF_RANGE("lfpsqp_projcg_diags");
     LF_ARG(ctx, ctx && Av);
-    BandOp bop;
-    LF_TRY(diags_op(ctx, a0, dg, off, K, dist, bop));
-    return projcg_impl(ctx, x, lambda, nullptr, nullptr, nullptr, Av, U, b, c, tol, maxit, n_global, flags, work, iters, nr, nullptr, &bop);
+    CoupledOp A;
+    LF_TRY(diags_op(ctx, "lfpsqp_projcg_diags", a0, dg, off, K, dist, A));
+    return projcg_coupled(ctx, x, lambda, A, Av, U, b, c, tol, maxit, n_global, flags, work, iters, nr);
 }
 
 extern "C" int lfpsqp_diags_mul(lfpsqp_ctx* ctx, double a0, const lfpsqp_vec* dg, const lfpsqp_mat* off, int64_t K, const int64_t* dist,
                                 const lfpsqp_vec* v, lfpsqp_vec* out) {
     LF_ARG(ctx, ctx);
-    BandOp bop;
-    LF_TRY(diags_op(ctx, a0, dg, off, K, dist, bop));
-    LF_ARG(ctx, v && out && v != out && v->p != out->p && out->n == v->n && (!dg || dg->n == v->n));
-    LF_ARG(ctx, bop.rows == v->n || v->n == lfpsqp_half_stride(bop.rows) + bop.rows);
-    if (ctx->comm_active())
-        return set_err(ctx, LFPSQP_ERR_UNSUPPORTED, "lfpsqp_diags_mul: one rank only (no halo exchange between row shards)");
-    return run_vec<DiagsMulF, 0, NoPost>(ctx, v->n, DiagsMulF{bop.diags(dg ? dg->p : nullptr, v->n, bop.rows), v->p, out->p, nullptr}, 0u, nullptr, NoPost());
+    CoupledOp A;
+    LF_TRY(diags_op(ctx, "lfpsqp_diags_mul", a0, dg, off, K, dist, A));
+    return coupled_mul_entry(ctx, A, v, out);
 }
 
 extern "C" int lfpsqp_projcg_op(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, lfpsqp_opfun A, void* user, lfpsqp_vec* Av,
@@ -2174,7 +2127,11 @@ extern "C" int lfpsqp_projcg_op(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lamb
                                 int64_t n_global, int flags, const lfpsqp_projcg_work* work, int64_t* iters, double* nr) {
     LF_RANGE("lfpsqp_projcg_op");
     LF_ARG(ctx, ctx && A && Av);
-    return projcg_impl(ctx, x, lambda, nullptr, A, user, Av, U, b, c, tol, maxit, n_global, flags, work, iters, nr);
+    PcgOperator op{PcgOperator::CALLBACK, lfpsqp_diag_op{0.0, nullptr}};
+    op.fn = A;
+    op.user = user;
+    op.Av = Av;
+    return projcg_impl(ctx, x, lambda, op, U, b, c, tol, maxit, n_global, flags, work, iters, nr);
 }
 
 extern "C" int lfpsqp_ctx_stream(lfpsqp_ctx* ctx, void** stream) {

@@ -114,6 +114,28 @@ def _amax_host(v):
     return float(np.max(np.abs(v), initial=0.0))
 
 
+def _coupled_operator(ctx, hess_lag_vec_):
+    """The Newton map of a Lagrangian Hessian that is diagonal plus couplings, or None.  Next to ``diag_`` the class exposes ONE of (looked for
+    in this order) ``offdiag`` (n-vector: :class:`TridiagonalOperator`), ``offdiags`` (N x bw matrix: :class:`BandedOperator`) or ``diagonals`` =
+    (dists, off) (:class:`DiagonalsOperator`); projcg_ keeps one pass per iteration with each unless DeviceOptions.tridiagonal_one_pass is off
+    (``fused``).  With bounds the Newton map is blockdiag(H + 2 lamy.*q, 2 lamy.*s) (src/inequality_helper.jl:144-158): the augmented diagonal
+    next to the same couplings on the x half.  The diagonal ``dg`` is the caller's to set: it is allocated with the work vectors."""
+    from .projcg import BandedOperator, DiagonalsOperator, TridiagonalOperator
+    if not hasattr(hess_lag_vec_, "diag_"):
+        return None
+    tri_off, band_off, diags_off = (getattr(hess_lag_vec_, name, None) for name in ("offdiag", "offdiags", "diagonals"))
+    if tri_off is not None:
+        op = TridiagonalOperator(0.0, None, tri_off)
+    elif band_off is not None:
+        op = BandedOperator(0.0, None, band_off, band_off.m)
+    elif diags_off is not None:
+        op = DiagonalsOperator(0.0, None, diags_off[1], diags_off[0])
+    else:
+        return None
+    op.fused = bool(getattr(ctx.options, "tridiagonal_one_pass", True))
+    return op
+
+
 def _allocate_projcg_work(ctx, n, m, ineq, Jct, factored, diagonal_hessian):
     """ProjCGWork (src/optimize.jl:214) and, unless the basis stays in factored form, the basis Z (:191) -- allocated TOGETHER and by trial
     (lfpsqp_vecs_alloc_placed / lfpsqp_basis_work_alloc_placed: the speed of the fused kernel is a property of the pair of allocations)."""
@@ -184,9 +206,8 @@ def optimize_core(f, grad_, c_, jac_, hess_lag_vec_, x0, xl, xu, m: int, param: 
     # their limits, or a sparse twin the nonzero path covers); where it cannot (LFPSQP_ONEPASS=-1, ld beyond the 32-bit lane offsets ...)
     # Z is materialised and every path has its two-pass form.
     # (a tridiagonal or banded Hessian sent through the callback path -- DeviceOptions.tridiagonal_one_pass off -- needs the materialised basis)
-    coupled_hessian = diagonal_hessian and (getattr(hess_lag_vec_, "offdiag", None) is not None or getattr(hess_lag_vec_, "offdiags", None) is not None
-                                            or getattr(hess_lag_vec_, "diagonals", None) is not None)
-    tri_callback = coupled_hessian and not bool(getattr(ctx.options, "tridiagonal_one_pass", True))
+    coupled = _coupled_operator(ctx, hess_lag_vec_)
+    tri_callback = coupled is not None and not coupled.fused
     factored = (bool(ctx.options.factored_basis) and diagonal_hessian and not tri_callback and 4 <= m <= 1024
                 and ctx.factored_basis_supported(Jct, getattr(c_, "Jsp", None)))
     # Allocation by trial costs tens of milliseconds (18 timed launches of F at n = 1e7, m = 128: 36 ms) and returns 3 % of every projected-CG
@@ -214,42 +235,19 @@ def optimize_core(f, grad_, c_, jac_, hess_lag_vec_, x0, xl, xu, m: int, param: 
     Wgen = np.zeros((m, m), order='F') if m > 0 else None                  # ksvd_'s small factor: Z == Jct @ Wgen
     ineqproject = InequalityDecompProject(idecomp) if ineq else None
 
-    # a TRIDIAGONAL Lagrangian Hessian: ``diag_`` fills the diagonal, ``offdiag`` (device n-vector, entry i couples variables i and i+1) holds the
-    # couplings -- projcg_ keeps one pass per iteration with it (lfpsqp_projcg_tridiag; one rank: the operator's own limit).  With bounds the
-    # Newton map is blockdiag(H + 2 lamy.*q, 2 lamy.*s) (src/inequality_helper.jl:144-158): the augmented diagonal (stacked, lfpsqp_augmented_diag
-    # or the tangent step, as for a diagonal Hessian) next to the same couplings on the x half
-    # A BANDED one (bandwidth 2 .. 4: second or higher differences) exposes ``offdiags`` instead, an N x bw device matrix whose column k-1 couples
-    # variables i and i+k: the same rules, lfpsqp_projcg_band
-    tri_off = getattr(hess_lag_vec_, "offdiag", None) if diagonal_hessian else None
-    band_off = getattr(hess_lag_vec_, "offdiags", None) if (diagonal_hessian and tri_off is None) else None
-    # A GRID-STENCIL one (a 2-D / 3-D field with a smoothness term) exposes ``diagonals`` = (dists, off): up to four off-diagonals at arbitrary
-    # distances, off an N x K device matrix whose column k-1 couples variables i and i + dists[k-1]: the same rules, lfpsqp_projcg_diags
-    diags_off = getattr(hess_lag_vec_, "diagonals", None) if (diagonal_hessian and tri_off is None and band_off is None) else None
-    if tri_off is not None or band_off is not None or diags_off is not None:
+    if coupled is not None:
         # (the tangent step's pass still hands projcg_ r0 and U'r0 -- neither involves A --, but never its folded initial projection, whose
         # sums are formed with the diagonal alone: init_fold stays off below)
-        if not bool(getattr(ctx.options, "tridiagonal_one_pass", True)):
+        if not coupled.fused:
             fuse_tangent = False              # (the callback path starts its solves itself)
         if getattr(Jct, "is_view", False) or ctx.nranks > 1:
             # lfpsqp_projcg_tridiag answers a matrix view or an active communicator with LFPSQP_ERR_UNSUPPORTED (the couplings would cross the
             # shard boundaries): those solves take the callback path, which makes its own start -- a start handed over by the one-pass tangent
             # step (start_given) could not be honoured there and projcg_ would raise
             fuse_tangent = False
-    if tri_off is not None:
-        from .projcg import TridiagonalOperator
         a_diag = projcgwork.placed_extra[0] if projcgwork.placed_extra else newvec()
-        newton_map = TridiagonalOperator(0.0, a_diag, tri_off)
-        newton_map.fused = bool(getattr(ctx.options, "tridiagonal_one_pass", True))
-    elif band_off is not None:
-        from .projcg import BandedOperator
-        a_diag = projcgwork.placed_extra[0] if projcgwork.placed_extra else newvec()
-        newton_map = BandedOperator(0.0, a_diag, band_off, band_off.m)
-        newton_map.fused = bool(getattr(ctx.options, "tridiagonal_one_pass", True))
-    elif diags_off is not None:
-        from .projcg import DiagonalsOperator
-        a_diag = projcgwork.placed_extra[0] if projcgwork.placed_extra else newvec()
-        newton_map = DiagonalsOperator(0.0, a_diag, diags_off[1], diags_off[0])
-        newton_map.fused = bool(getattr(ctx.options, "tridiagonal_one_pass", True))
+        newton_map = coupled
+        newton_map.dg = a_diag
     elif diagonal_hessian:
         a_diag = projcgwork.placed_extra[0] if projcgwork.placed_extra else newvec()
         newton_map = DiagOperator(0.0, a_diag)
@@ -350,7 +348,7 @@ def optimize_core(f, grad_, c_, jac_, hess_lag_vec_, x0, xl, xu, m: int, param: 
                 # (flag 1 = LFPSQP_TANGENT_INIT_PROJCG: the pass is projcg!'s initial projection as well -- src/projcg.jl:58-62 -- with U'r0 from
                 # the Gram matrix; projcg_ then starts with its first iteration, start_projected=True.  Only where the Gram matrix resolves
                 # I - U'U: a full-rank block with cond^2 <= 10, the fast path of the factorisation; otherwise projcg_ measures U'r0 itself)
-                init_fold = bool(tri_off is None and band_off is None and diags_off is None and rank == m and S_[0] * S_[0] <= 10.0 * S_[m - 1] * S_[m - 1])
+                init_fold = bool(coupled is None and rank == m and S_[0] * S_[0] <= 10.0 * S_[m - 1] * S_[m - 1])
                 ctx.check(ctx.L.lfpsqp_tangent_step(ctx.h, C.byref(bs), sig_c.ctypes.data, vt_c.ctypes.data, m, Jtd.ctypes.data, Ggram.ctypes.data, d.h,
                                                     C.byref(cc) if cc is not None else None, x.h, a_diag.h,
                                                     C.byref(idc) if ineq else None, hx.h if ineq else None, idecomp.S.h if ineq else None,

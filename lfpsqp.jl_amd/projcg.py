@@ -94,54 +94,19 @@ class LowRankOperator:
         return self
 
 
-class TridiagonalOperator:
-    """(A v)_i = (a0 + dg_i) v_i + off_{i-1} v_{i-1} + off_i v_{i+1} (lfpsqp_tridiag_op): a diagonal Hessian plus nearest-neighbour
-    couplings.  ``off``: DeviceVector of length n (entry i couples rows i and i+1; the last entry is ignored).  On a :class:`DeviceBasis`
-    projcg_ runs it on the fused ONE-pass iteration (lfpsqp_projcg_tridiag); ``mul_`` is the operator on its own (lfpsqp_tridiag_mul), which
-    the generic loop / lfpsqp_projcg_op use -- two passes over the basis per iteration.
-    With bounds (a stacked basis, :class:`InequalityDecompProject`): ``dg`` is a :class:`StackedVector` (the augmented diagonal, both halves)
-    and ``off`` has N entries, the couplings of the x half -- the Newton map blockdiag(T, diag) of src/inequality_helper.jl:144-158, on the same
-    one-pass iteration."""
+class _CoupledOperator:
+    """A = a0*I + diag(dg) + symmetric off-diagonal couplings ``off``: what :class:`TridiagonalOperator`, :class:`BandedOperator` and
+    :class:`DiagonalsOperator` share.  A subclass supplies the two C calls: ``_mul`` (the operator on its own) and ``_solve`` (the fused ONE-pass
+    projected CG; ``head`` and ``tail`` are the arguments before and after the operator's own).  ``fused = False`` sends projcg_ to the callback
+    path (the generic loop / lfpsqp_projcg_op with ``mul_``: two passes over the basis per iteration)."""
 
-    def __init__(self, a0: float, dg: DeviceVector | None, off: DeviceVector):
+    def __init__(self, a0: float, dg: DeviceVector | None, off):
         self.a0, self.dg, self.off = float(a0), dg, off
-        self._tmp = None
-
-    def _c(self):
-        return _capi.TridiagOp(self.a0, self.dg.h if self.dg is not None else None, self.off.h)
-
-    def mul_(self, dest: DeviceVector, v: DeviceVector, a=None, b=None):
-        ctx = dest.ctx
-        a_c = self._c()
-        if a is None:
-            ctx.check(ctx.L.lfpsqp_tridiag_mul(ctx.h, C.byref(a_c), v.h, dest.h))
-            return dest
-        if self._tmp is None or self._tmp.n != dest.n:
-            self._tmp = DeviceVector(ctx, dest.n)
-        ctx.check(ctx.L.lfpsqp_tridiag_mul(ctx.h, C.byref(a_c), v.h, self._tmp.h))
-        waxpby(a, self._tmp, b, dest, dest)
-        return dest
-
-    def adjoint(self):
-        return self
-
-
-class BandedOperator:
-    """(A v)_i = (a0 + dg_i) v_i + sum_{k=1..bw} (off_k[i-k] v_{i-k} + off_k[i] v_{i+k}), 1 <= bw <= 4: a diagonal Hessian plus couplings up to
-    ``bw`` rows apart (second or higher differences: Whittaker / Hodrick-Prescott smoothing, curvature penalties).  ``off``: DeviceMatrix with n
-    rows and at least ``bw`` columns, column k-1 = off_k (entry i couples rows i and i+k; entries with i + k >= n are ignored).  On a
-    :class:`DeviceBasis` projcg_ runs it on the fused ONE-pass iteration (lfpsqp_projcg_band; bw = 1 is the tridiagonal path, bit for bit);
-    ``mul_`` is the operator on its own (lfpsqp_band_mul), which the generic loop / lfpsqp_projcg_op use -- two passes over the basis per
-    iteration.  ``fused = False`` sends projcg_ to that callback path.  With bounds (a stacked basis): ``dg`` is a :class:`StackedVector` and
-    ``off`` has N rows, the couplings of the x half, as for :class:`TridiagonalOperator`."""
-
-    def __init__(self, a0: float, dg: DeviceVector | None, off: DeviceMatrix, bw: int):
-        self.a0, self.dg, self.off, self.bw = float(a0), dg, off, int(bw)
         self.fused = True
         self._tmp = None
 
-    def _mul(self, ctx, v, out):
-        return ctx.L.lfpsqp_band_mul(ctx.h, self.a0, self.dg.h if self.dg is not None else None, self.off.h, self.bw, v.h, out.h)
+    def _dg_h(self):
+        return self.dg.h if self.dg is not None else None
 
     def mul_(self, dest: DeviceVector, v: DeviceVector, a=None, b=None):
         ctx = dest.ctx
@@ -158,7 +123,51 @@ class BandedOperator:
         return self
 
 
-class DiagonalsOperator:
+class TridiagonalOperator(_CoupledOperator):
+    """(A v)_i = (a0 + dg_i) v_i + off_{i-1} v_{i-1} + off_i v_{i+1} (lfpsqp_tridiag_op): a diagonal Hessian plus nearest-neighbour
+    couplings.  ``off``: DeviceVector of length n (entry i couples rows i and i+1; the last entry is ignored).  On a :class:`DeviceBasis`
+    projcg_ runs it on the fused ONE-pass iteration (lfpsqp_projcg_tridiag); ``mul_`` is the operator on its own (lfpsqp_tridiag_mul), which
+    the generic loop / lfpsqp_projcg_op use -- two passes over the basis per iteration.
+    With bounds (a stacked basis, :class:`InequalityDecompProject`): ``dg`` is a :class:`StackedVector` (the augmented diagonal, both halves)
+    and ``off`` has N entries, the couplings of the x half -- the Newton map blockdiag(T, diag) of src/inequality_helper.jl:144-158, on the same
+    one-pass iteration."""
+
+    def __init__(self, a0: float, dg: DeviceVector | None, off: DeviceVector):
+        super().__init__(a0, dg, off)
+
+    def _c(self):
+        return _capi.TridiagOp(self.a0, self._dg_h(), self.off.h)
+
+    def _mul(self, ctx, v, out):
+        a_c = self._c()
+        return ctx.L.lfpsqp_tridiag_mul(ctx.h, C.byref(a_c), v.h, out.h)
+
+    def _solve(self, ctx, head, tail):
+        a_c = self._c()
+        return ctx.L.lfpsqp_projcg_tridiag(*head, C.byref(a_c), *tail)
+
+
+class BandedOperator(_CoupledOperator):
+    """(A v)_i = (a0 + dg_i) v_i + sum_{k=1..bw} (off_k[i-k] v_{i-k} + off_k[i] v_{i+k}), 1 <= bw <= 4: a diagonal Hessian plus couplings up to
+    ``bw`` rows apart (second or higher differences: Whittaker / Hodrick-Prescott smoothing, curvature penalties).  ``off``: DeviceMatrix with n
+    rows and at least ``bw`` columns, column k-1 = off_k (entry i couples rows i and i+k; entries with i + k >= n are ignored).  On a
+    :class:`DeviceBasis` projcg_ runs it on the fused ONE-pass iteration (lfpsqp_projcg_band; bw = 1 is the tridiagonal path, bit for bit);
+    ``mul_`` is the operator on its own (lfpsqp_band_mul), which the generic loop / lfpsqp_projcg_op use -- two passes over the basis per
+    iteration.  ``fused = False`` sends projcg_ to that callback path.  With bounds (a stacked basis): ``dg`` is a :class:`StackedVector` and
+    ``off`` has N rows, the couplings of the x half, as for :class:`TridiagonalOperator`."""
+
+    def __init__(self, a0: float, dg: DeviceVector | None, off: DeviceMatrix, bw: int):
+        super().__init__(a0, dg, off)
+        self.bw = int(bw)
+
+    def _mul(self, ctx, v, out):
+        return ctx.L.lfpsqp_band_mul(ctx.h, self.a0, self._dg_h(), self.off.h, self.bw, v.h, out.h)
+
+    def _solve(self, ctx, head, tail):
+        return ctx.L.lfpsqp_projcg_band(*head, self.a0, self._dg_h(), self.off.h, self.bw, *tail)
+
+
+class DiagonalsOperator(_CoupledOperator):
     """(A v)_i = (a0 + dg_i) v_i + sum_k (off_k[i - s_k] v_{i - s_k} + off_k[i] v_{i + s_k}) for 1 <= K <= 4 off-diagonals at ARBITRARY distances
     ``dists`` = (s_1 < ... < s_K): the Hessian of a smoothness / diffusion term on a 2-D or 3-D field in row-major order ((1, nx), (1, nx, nx ny),
     (1, nx - 1, nx, nx + 1) for the 5-, 7- and 9-point stencils; :func:`lfpsqp_jl_amd.problems.grid_laplacian`).  ``off``: DeviceMatrix with n
@@ -169,29 +178,15 @@ class DiagonalsOperator:
     ``off`` has N rows, the couplings of the x half, as for :class:`BandedOperator`."""
 
     def __init__(self, a0: float, dg: DeviceVector | None, off: DeviceMatrix, dists):
-        self.a0, self.dg, self.off = float(a0), dg, off
+        super().__init__(a0, dg, off)
         self.dists = tuple(int(s) for s in dists)
         self._dist_c = (_capi.c_i64 * max(len(self.dists), 1))(*self.dists)
-        self.fused = True
-        self._tmp = None
 
     def _mul(self, ctx, v, out):
-        return ctx.L.lfpsqp_diags_mul(ctx.h, self.a0, self.dg.h if self.dg is not None else None, self.off.h, len(self.dists), self._dist_c,
-                                      v.h, out.h)
+        return ctx.L.lfpsqp_diags_mul(ctx.h, self.a0, self._dg_h(), self.off.h, len(self.dists), self._dist_c, v.h, out.h)
 
-    def mul_(self, dest: DeviceVector, v: DeviceVector, a=None, b=None):
-        ctx = dest.ctx
-        if a is None:
-            ctx.check(self._mul(ctx, v, dest))
-            return dest
-        if self._tmp is None or self._tmp.n != dest.n:
-            self._tmp = DeviceVector(ctx, dest.n)
-        ctx.check(self._mul(ctx, v, self._tmp))
-        waxpby(a, self._tmp, b, dest, dest)
-        return dest
-
-    def adjoint(self):
-        return self
+    def _solve(self, ctx, head, tail):
+        return ctx.L.lfpsqp_projcg_diags(*head, self.a0, self._dg_h(), self.off.h, len(self.dists), self._dist_c, *tail)
 
 
 class DeviceBasis:
@@ -334,42 +329,16 @@ def projcg_(x: DeviceVector, lam: DeviceVector | None, A, U, b: DeviceVector, c:
         if rc != -5:                 # LFPSQP_ERR_UNSUPPORTED (a shape without the one-pass iteration): the callback path below
             ctx.check(rc)
             return iters.value, nr.value
-    if isinstance(A, TridiagonalOperator) and (isinstance(U, DeviceBasis) or stacked) and not (resume or start_projected) and getattr(A, "fused", True):
-        if getattr(work, "Av", None) is None:
-            work.Av = DeviceVector(ctx, n)
-        iters = _capi.c_i64()
-        nr = C.c_double()
-        a_c, u_c, w_c = A._c(), U._c(), work._c()
-        flags = (WANT_LAMBDA if (want_lambda and lam is not None) else 0) | (START_GIVEN if start_given else 0)
-        rc = ctx.L.lfpsqp_projcg_tridiag(ctx.h, x.h, lam.h if lam is not None else None, C.byref(a_c), work.Av.h, C.byref(u_c), b.h,
-                                         c.h if c is not None else None, float(tol), int(maxit), int(n_global), flags,
-                                         C.byref(w_c), C.byref(iters), C.byref(nr))
-        if rc != -5 or start_given:  # LFPSQP_ERR_UNSUPPORTED (no one-pass iteration for this shape / more than one rank): the callback path below
-            ctx.check(rc)
-            return iters.value, nr.value
-    if isinstance(A, BandedOperator) and (isinstance(U, DeviceBasis) or stacked) and not (resume or start_projected) and A.fused:
+    if isinstance(A, _CoupledOperator) and (isinstance(U, DeviceBasis) or stacked) and not (resume or start_projected) and A.fused:
         if getattr(work, "Av", None) is None:
             work.Av = DeviceVector(ctx, n)
         iters = _capi.c_i64()
         nr = C.c_double()
         u_c, w_c = U._c(), work._c()
         flags = (WANT_LAMBDA if (want_lambda and lam is not None) else 0) | (START_GIVEN if start_given else 0)
-        rc = ctx.L.lfpsqp_projcg_band(ctx.h, x.h, lam.h if lam is not None else None, A.a0, A.dg.h if A.dg is not None else None, A.off.h,
-                                      A.bw, work.Av.h, C.byref(u_c), b.h, c.h if c is not None else None, float(tol), int(maxit),
-                                      int(n_global), flags, C.byref(w_c), C.byref(iters), C.byref(nr))
-        if rc != -5 or start_given:  # LFPSQP_ERR_UNSUPPORTED (no one-pass iteration for this shape / more than one rank): the callback path below
-            ctx.check(rc)
-            return iters.value, nr.value
-    if isinstance(A, DiagonalsOperator) and (isinstance(U, DeviceBasis) or stacked) and not (resume or start_projected) and A.fused:
-        if getattr(work, "Av", None) is None:
-            work.Av = DeviceVector(ctx, n)
-        iters = _capi.c_i64()
-        nr = C.c_double()
-        u_c, w_c = U._c(), work._c()
-        flags = (WANT_LAMBDA if (want_lambda and lam is not None) else 0) | (START_GIVEN if start_given else 0)
-        rc = ctx.L.lfpsqp_projcg_diags(ctx.h, x.h, lam.h if lam is not None else None, A.a0, A.dg.h if A.dg is not None else None, A.off.h,
-                                       len(A.dists), A._dist_c, work.Av.h, C.byref(u_c), b.h, c.h if c is not None else None, float(tol),
-                                       int(maxit), int(n_global), flags, C.byref(w_c), C.byref(iters), C.byref(nr))
+        rc = A._solve(ctx, (ctx.h, x.h, lam.h if lam is not None else None),
+                      (work.Av.h, C.byref(u_c), b.h, c.h if c is not None else None, float(tol), int(maxit), int(n_global), flags,
+                       C.byref(w_c), C.byref(iters), C.byref(nr)))
         if rc != -5 or start_given:  # LFPSQP_ERR_UNSUPPORTED (no one-pass iteration for this shape / more than one rank): the callback path below
             ctx.check(rc)
             return iters.value, nr.value
