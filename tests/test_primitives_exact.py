@@ -26,19 +26,13 @@ import pytest
 import lfpsqp_jl_amd as L
 from lfpsqp_jl_amd.device import nrm2_head
 from lfpsqp_jl_amd.inequality import StackedVector
+from tests.helpers import POISON, U, bits, fsum, gamma, ints, short_reals
 
-U = 2.0 ** -53                                   # unit roundoff of binary64
 SIZES = [1, 2, 3, 511, 512, 513, 1023, 1025, 2047, 2048, 2049, 4097]
 GEMV_M = [1, 3, 4, 5, 96, 97, 128, 132, 133, 257]
 GEMV_N = [1, 3, 1023, 1025, 2049, 4100]
 BIG = 2.0 ** 20                                  # the sentinel
-POISON = -1.2345678912345e+77                    # (a value no operation here produces)
 TILE = 512                                       # rows per vec_kernel tile (kSlabRows)
-
-
-def gamma(k):
-    """gamma_k = k u / (1 - k u): k roundings compound to a relative error of at most this (Higham, Accuracy and Stability, 3.1)."""
-    return Fraction(k) * Fraction(U) / (1 - Fraction(k) * Fraction(U))
 
 
 def rnd(q):
@@ -48,14 +42,6 @@ def rnd(q):
 
 def fma(a, b, c):
     return rnd(Fraction(a) * Fraction(b) + Fraction(c))
-
-
-def fsum(a):
-    return math.fsum(np.asarray(a, dtype=np.float64).tolist())
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 def counts_of(n):
@@ -68,25 +54,10 @@ def positions_of(n, count):
     return sorted({p for p in (0, count - 1, count, n - 1, 511, 512, 513, 2047, 2048, 2049) if 0 <= p < n})
 
 
-def ints(seed, shape, lim=1024):
-    """Integers in [-lim, lim], about a quarter of them zero, as binary64."""
-    rng = np.random.default_rng(seed)
-    a = rng.integers(-lim, lim + 1, size=shape)
-    a[rng.random(size=shape) < 0.25] = 0
-    return a.astype(np.float64)
-
-
 def reals(seed, n, emin=-30, emax=30):
     """Full 53-bit mantissas, both signs, binary exponents spread over [emin, emax]."""
     rng = np.random.default_rng(seed)
     return np.ldexp(rng.uniform(1.0, 2.0, n) * rng.choice([-1.0, 1.0], n), rng.integers(emin, emax + 1, n))
-
-
-def short_reals(seed, n, emin=-30, emax=30):
-    """The same with 26 significant bits, so that the product of two of them is exact."""
-    rng = np.random.default_rng(seed)
-    mant = rng.integers(2 ** 25, 2 ** 26, n).astype(np.float64)
-    return np.ldexp(mant * rng.choice([-1.0, 1.0], n), rng.integers(emin, emax + 1, n) - 25)
 
 
 # ---- thin wrappers over the entry points that the object layer does not expose -------------------------------------------------
