@@ -208,8 +208,8 @@ int lfpsqp_allreduce(lfpsqp_ctx* ctx, lfpsqp_vec* v, int64_t count);
 
 /* ---- sparse constraint gradients (the reference's README.md:80 to-do) ---------------------- */
 /* Jct with a few nonzeros per ROW (every variable in a few constraints; e.g. the system of test/test_retractions.jl:34-54).
- * Built from host triplets (0-based LOCAL row, column, value; duplicates add up; any order); at most 256 nonzeros per
- * row.  Stored twice on the device: ELL by rows for Jct*t (row-local) and CSC cut into fixed chunks for Jct'*v
+ * Built from host triplets (0-based LOCAL row, column, value; duplicates add up; any order); at most 256 distinct positions per
+ * row (counted after the duplicates are merged: 256 is accepted, 257 is answered with LFPSQP_ERR_UNSUPPORTED).  Stored twice on the device: ELL by rows for Jct*t (row-local) and CSC cut into fixed chunks for Jct'*v
  * (fixed-order sums, no atomics: bit-reproducible); both products move nnz*(8+4) bytes instead of 8*n*m.
  * A handle in lfpsqp_constraints.Jsp / lfpsqp_basis.S makes lfpsqp_constraints_eval and lfpsqp_pcg use them. */
 int lfpsqp_spmat_create(lfpsqp_ctx* ctx, int64_t n, int64_t m, int64_t nnz, const int64_t* rows, const int64_t* cols,
@@ -222,10 +222,13 @@ int lfpsqp_spmv_n(lfpsqp_ctx* ctx, const lfpsqp_spmat* S, double alpha, const lf
 /* A second object with the STRUCTURE of S (same rows / columns, shared on the device) and its own copy of the values: the
  * x-dependent constraint gradients diag(phi'(x)) A of lfpsqp_elementwise, rescaled in place by lfpsqp_spmat_rowscale. */
 int lfpsqp_spmat_clone(lfpsqp_ctx* ctx, const lfpsqp_spmat* S, lfpsqp_spmat** out);
-/* dst.values = diag(v) * src.values (v: n-vector); dst is src itself or a clone of it */
+/* dst.values = diag(v) * src.values (v: n-vector, >= S.n entries); dst is src itself or a clone of it.  Both stored copies of dst (ELL and
+ * CSC) receive the same products of SRC's values: scaling a clone twice scales src twice, not the previous result. */
 int lfpsqp_spmat_rowscale(lfpsqp_ctx* ctx, lfpsqp_spmat* dst, const lfpsqp_spmat* src, const lfpsqp_vec* v);
 /* M[:, 0:m) = S as a dense matrix (the tangent setup -- lfpsqp_factorize, whose basis Z is dense anyway -- and the Newton
- * retraction keep using the dense kernels) */
+ * retraction keep using the dense kernels).  M is a plain matrix (no view) with rows(M) == S.n and cols(M) >= S.m: the columns
+ * [0, S.m) are overwritten (zero where S has no entry; a position whose duplicates sum to zero holds that zero), the columns
+ * from S.m on are LEFT ALONE -- lfpsqp_constraints_jac relies on it for the ball column of Jct. */
 int lfpsqp_spmat_to_dense(lfpsqp_ctx* ctx, const lfpsqp_spmat* S, lfpsqp_mat* M);
 /* G (host, M x M column-major) = A' diag(w2) A for A = [S | Jct[:, S.m : Jct.m)] (Jct NULL: A = S, M = S.m; w2 NULL: no weights), summed
  * over the ranks: the Gram matrix of the tangent setup from the NONZEROS.  The scattered accumulation is exact (every term cut into two
@@ -578,7 +581,10 @@ typedef struct lfpsqp_elementwise {
  * column m_lin is the ball gradient [2x; -1] (refreshed by lfpsqp_constraints_jac) and the
  * inequality x'x <= R2 has been turned into an equality with a slack variable
  * (src/optimize.jl:23-51).  n_x / slack_row are LOCAL row indices on this rank
- * (slack_row = -1 if another rank owns the slack variable). */
+ * (slack_row = -1 if another rank owns the slack variable; otherwise n_x <= slack_row < rows(Jct)).
+ * slack_row means something with has_ball ONLY: without a ball it is ignored by every entry point -- the common quadratic term
+ * qw * sum_{i < n_x} x_i^2 of lfpsqp_elementwise has no slack variable, whatever slack_row holds.  Rows from n_x on other than
+ * slack_row, and everything beyond rows(Jct) in x / kind / hx, reach no result and are not written. */
 typedef struct lfpsqp_constraints {
     const lfpsqp_mat* Jct;
     int64_t m_lin;

@@ -665,6 +665,10 @@ static bool ew_onepass_ok(const lfpsqp_ctx* ctx, const lfpsqp_constraints* cons)
     return ew && !ew->Asp && ew->A && !cons->has_ball && cons->m_lin >= 4 && onepass_cw(ctx, (int)cons->m_lin, ew->A->ld, cons->Jct->n) != 0;
 }
 
+// slack_row has a meaning with has_ball only (lfpsqp_hip.h): the common quadratic term of lfpsqp_elementwise shares the ball's partial sum but has
+// no slack variable -- jac! and the Hessian diagonal never looked at slack_row there, and c! / the Newton steps must not either
+static inline int64_t cons_slack(const lfpsqp_constraints* c) { return c->has_ball ? c->slack_row : -1; }
+
 // raw[0:m_lin) = the constraint products (J x, or A' phi(x)), raw[m_lin] = sum_{i<n_x} x_i^2 - x[slack_row] (when the class has a ball or a
 // common quadratic term) -- device buffer, all-reduced, stream-ordered.  `x` has >= rows(Jct) entries.
 static int cons_raw(lfpsqp_ctx* ctx, const lfpsqp_constraints* cons, const double* x, double* raw) {
@@ -674,7 +678,7 @@ static int cons_raw(lfpsqp_ctx* ctx, const lfpsqp_constraints* cons, const doubl
     const lfpsqp_elementwise* ew = cons->ew;
     const bool quad = cons->has_ball || (ew && ew->qw);
     if (ew) {
-        const EwEvalE ee{x, ew->kind ? ew->kind->p : nullptr, ew->Asp ? ew->work->p : nullptr, cons->n_x, cons->slack_row, quad ? 1 : 0};
+        const EwEvalE ee{x, ew->kind ? ew->kind->p : nullptr, ew->Asp ? ew->work->p : nullptr, cons->n_x, cons_slack(cons), quad ? 1 : 0};
         if (ew->Asp) {
             LF_TRY((run_vec<EwEvalVecF, 1, NoPost>(ctx, N, EwEvalVecF{ee}, 0u, raw + ml, NoPost())));
             return spmv_t(ctx, ew->Asp, ew->work->p, raw);
@@ -686,7 +690,7 @@ static int cons_raw(lfpsqp_ctx* ctx, const lfpsqp_constraints* cons, const doubl
                 LF_HIP(ctx, hipMalloc((void**)&ctx->d_zeros, sizeof(double) * (kOnepassMaxCols + 8)));
                 LF_HIP(ctx, hipMemsetAsync(ctx->d_zeros, 0, sizeof(double) * (kOnepassMaxCols + 8), ctx->stream));
             }
-            NRStepE e0{const_cast<double*>(x), nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, cons->n_x, cons->slack_row, quad ? 1 : 0,
+            NRStepE e0{const_cast<double*>(x), nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, cons->n_x, cons_slack(cons), quad ? 1 : 0,
                        ctx->istat};
             e0.kind = ew->kind ? ew->kind->p : nullptr;
             e0.ew_one = 1;
@@ -697,7 +701,7 @@ static int cons_raw(lfpsqp_ctx* ctx, const lfpsqp_constraints* cons, const doubl
     }
     if (ml > 0 && cons->Jsp) LF_TRY(spmv_t(ctx, cons->Jsp, x, raw));                       // c! streams the nonzeros
     else if (ml > 0) LF_TRY(run_gemv_t(ctx, J, ml, N, PlainVec{x}, raw));
-    if (cons->has_ball) LF_TRY((run_vec<BallF, 1, NoPost>(ctx, N, BallF{x, cons->n_x, cons->slack_row}, 0u, raw + ml, NoPost())));
+    if (cons->has_ball) LF_TRY((run_vec<BallF, 1, NoPost>(ctx, N, BallF{x, cons->n_x, cons_slack(cons)}, 0u, raw + ml, NoPost())));
     return 0;
 }
 
@@ -900,7 +904,7 @@ int lfpsqp_constraints_jac(lfpsqp_ctx* ctx, const lfpsqp_constraints* cons, cons
         }
     }
     if (cons->has_ball)
-        LF_TRY((run_vec<BallColF, 0, NoPost>(ctx, Jct->n, BallColF{x->p, Jct->p + cons->m_lin * Jct->ld, cons->n_x, cons->slack_row}, 0u,
+        LF_TRY((run_vec<BallColF, 0, NoPost>(ctx, Jct->n, BallColF{x->p, Jct->p + cons->m_lin * Jct->ld, cons->n_x, cons_slack(cons)}, 0u,
                                              nullptr, NoPost())));
     if (!cval) return 0;                                      // gradients only: the caller holds c(x) already (an accepted retraction returns it)
     return cons_eval(ctx, cons, x, cval);
@@ -989,7 +993,7 @@ int lfpsqp_retract_nr(lfpsqp_ctx* ctx, const lfpsqp_basis* U, const double* Sigm
         LF_HIP(ctx, hipEventRecord(ctx->ev_slot[0], ctx->stream));
         NRStepE ep{xnew->p, x->p, ineq ? lfpsqp_half_stride(N) : 0, ineq ? U->sx->p : nullptr, ineq ? U->sy->p : nullptr,
                    ineq ? idata->q->p : nullptr, ineq ? idata->r->p : nullptr, ineq ? idata->s->p : nullptr,
-                   ineq ? idata->t->p : nullptr, cons->n_x, cons->slack_row, quad ? 1 : 0, ctx->istat};
+                   ineq ? idata->t->p : nullptr, cons->n_x, cons_slack(cons), quad ? 1 : 0, ctx->istat};
         if (ew) {
             ep.kind = ew->kind ? ew->kind->p : nullptr;
             ep.phi_out = ew->Asp ? ew->work->p : nullptr;      // (identity phi with a sparse A: the product reads xnew itself)
@@ -1025,7 +1029,7 @@ int lfpsqp_retract_nr(lfpsqp_ctx* ctx, const lfpsqp_basis* U, const double* Sigm
             else if (cwd) LF_TRY((run_onepass<NRStepRow<false>, 1, 1>(ctx, cons->Jct, wm, ml, N, dwdelta, NRStepRow<false>{ep}, draw, 4)));
             else if (ew && ew->Asp) {                             // sparse A without the generator hint: dense step over Z, sparse c!
                 LF_TRY((run_gemv_nt<NRStepE, 0>(ctx, s1, n1, t1, nullptr, 0, N, ep, draw + ml)));
-                if (quad) LF_TRY((run_vec<BallF, 1, NoPost>(ctx, N, BallF{xnew->p, cons->n_x, cons->slack_row}, 0u, draw + ml, NoPost())));   // (summed as c! sums it)
+                if (quad) LF_TRY((run_vec<BallF, 1, NoPost>(ctx, N, BallF{xnew->p, cons->n_x, cons_slack(cons)}, 0u, draw + ml, NoPost())));   // (summed as c! sums it)
                 LF_TRY(spmv_t(ctx, csp, ep.phi_out ? ep.phi_out : xnew->p, draw));
             } else if (quad || ew) LF_TRY((run_gemv_nt<NRStepE, 1>(ctx, s1, n1, t1, cmat, ml, N, ep, draw)));
             else LF_TRY((run_gemv_nt<NRStepE, 0>(ctx, s1, n1, t1, cmat, ml, N, ep, draw)));
@@ -1088,7 +1092,7 @@ int lfpsqp_retract_nr(lfpsqp_ctx* ctx, const lfpsqp_basis* U, const double* Sigm
             const int64_t N = cons->Jct->n;
             NRStepE ep{xnew->p, x->p, ineq ? lfpsqp_half_stride(N) : 0, ineq ? U->sx->p : nullptr, ineq ? U->sy->p : nullptr,
                        ineq ? idata->q->p : nullptr, ineq ? idata->r->p : nullptr, ineq ? idata->s->p : nullptr,
-                       ineq ? idata->t->p : nullptr, cons->n_x, cons->slack_row, cons->has_ball ? 1 : 0, ctx->istat};
+                       ineq ? idata->t->p : nullptr, cons->n_x, cons_slack(cons), cons->has_ball ? 1 : 0, ctx->istat};
             ctx->h_istat[I_NR_STATUS] = 0;
             LF_HIP(ctx, hipMemsetAsync(ctx->istat + I_NR_STATUS, 0, sizeof(int64_t), ctx->stream));
             LF_TRY((run_gemv_nt<NRStepE, 1>(ctx, U->Z, m, tv.p, cons->Jct, ml, N, ep, ctx->d_m)));
@@ -1216,14 +1220,14 @@ int lfpsqp_retract_nr_batch(lfpsqp_ctx* ctx, const lfpsqp_basis* U, const double
     }
     const NRStepE ep{xnew[0]->p, x->p, ineq ? lfpsqp_half_stride(N) : 0, ineq ? U->sx->p : nullptr, ineq ? U->sy->p : nullptr,
                      ineq ? idata->q->p : nullptr, ineq ? idata->r->p : nullptr, ineq ? idata->s->p : nullptr,
-                     ineq ? idata->t->p : nullptr, cons->n_x, cons->slack_row, cons->has_ball ? 1 : 0, ctx->istat};
+                     ineq ? idata->t->p : nullptr, cons->n_x, cons_slack(cons), cons->has_ball ? 1 : 0, ctx->istat};
     for (int b = 0; b < nb; ++b) {                                                                  // :116-124 per trial
         LF_TRY(lfpsqp_vec_copy(ctx, xnew[b], xtilde[b]));
         if (ineq) LF_TRY(lfpsqp_y_retract(ctx, xnew[b], x, idata));
         if (mfma) continue;                       // c! of all trial points in ONE pass over Jct, below
         if (ml > 0) LF_TRY(run_gemv_t(ctx, cons->Jct, ml, N, PlainVec{xnew[b]->p}, draw + (size_t)b * ml));
         if (cons->has_ball)
-            LF_TRY((run_vec<BallF, 1, NoPost>(ctx, N, BallF{xnew[b]->p, cons->n_x, cons->slack_row}, 0u, draw + (size_t)NBk * ml + b, NoPost())));
+            LF_TRY((run_vec<BallF, 1, NoPost>(ctx, N, BallF{xnew[b]->p, cons->n_x, cons_slack(cons)}, 0u, draw + (size_t)NBk * ml + b, NoPost())));
     }
     if (mfma) {
         // the step kernel with zero coefficients and nothing updated or stored (eval_only): its second product and ball partials ARE c! at the

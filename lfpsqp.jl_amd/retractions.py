@@ -77,7 +77,8 @@ class ElementwiseConstraints(DeviceConstraints):
     with constraint gradients Jct(x) = diag(phi'(x)) A + 2 x qw' refreshed in place by ``jac_`` (the reference's jac!,
     src/autodiff_generators.jl:60-66) and a DIAGONAL Lagrangian-Hessian term (``hess_diag_``; hess_lag_vec!, :80-104).
     Covers the reference's own nonlinear test systems (test/test_retractions.jl:1-54, see :func:`sin_system_constraints` /
-    :func:`sphere_system_constraints`).  ``A``: DeviceMatrix (n x m), or a SparseMatrix -- then c!, jac!, the tangent setup, the
+    :func:`sphere_system_constraints`).  ``slack_row`` belongs to the ball (``has_ball``): without one it is ignored -- the quadratic
+    term has no slack variable.  ``A``: DeviceMatrix (n x m), or a SparseMatrix -- then c!, jac!, the tangent setup, the
     Newton steps and the inner solves of ProjPenalty all stream the nonzeros.  ``Jct`` (n x (m + ball)) is the working matrix.
 
     ``stream`` (dense ``A`` with a ``kind`` and / or ``qw``, no ball; default: whenever the library's one-pass kernels cover the shape): the

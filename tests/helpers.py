@@ -3,7 +3,8 @@ from fractions import Fraction
 
 import numpy as np
 
-# ---- shared by the exact-reference suites (tests/test_primitives_exact.py, tests/test_matrix_cores_exact.py) -----------------------
+# ---- shared by the exact-reference suites (tests/test_primitives_exact.py, tests/test_matrix_cores_exact.py,
+#      tests/test_constraints_exact.py) ------------------------------------------------------------------------------------------------
 U = 2.0 ** -53                                   # unit roundoff of binary64
 POISON = -1.2345678912345e+77                    # (a value no operation here produces)
 
@@ -35,6 +36,24 @@ def short_reals(seed, n, emin=-30, emax=30, nbits=26):
     rng = np.random.default_rng(seed)
     mant = rng.integers(2 ** (nbits - 1), 2 ** nbits, n).astype(np.float64)
     return np.ldexp(mant * rng.choice([-1.0, 1.0], n), rng.integers(emin, emax + 1, n) - (nbits - 1))
+
+
+def i64(a):
+    """Integer-valued binary64 data as int64 (checked)."""
+    a = np.asarray(a)
+    out = a.astype(np.int64)
+    assert np.array_equal(out, a)
+    return out
+
+
+def imatmul(A, B):
+    """int64 A @ B with both operands contiguous (numpy's integer product crawls on a transposed view)."""
+    return np.ascontiguousarray(A) @ np.ascontiguousarray(B)
+
+
+def ulp(v):
+    """The spacing of binary64 at |v| (v != 0, normal range): 2^(floor(log2 |v|) - 52)."""
+    return math.ldexp(1.0, math.frexp(float(v))[1] - 53)
 
 
 class DiagOpRef:

@@ -25,7 +25,7 @@ import numpy as np
 import pytest
 
 import lfpsqp_jl_amd as L
-from tests.helpers import POISON, bits, gamma, ints, short_reals
+from tests.helpers import POISON, bits, gamma, i64, imatmul, ints, short_reals
 
 BIG = 2.0 ** 20                                  # the sentinel
 SQUARES = np.array([0.0, 1.0, 4.0, 9.0])
@@ -35,19 +35,6 @@ LIM = 16                                         # |entries| of the integer matr
 def weights(seed, n):
     """Perfect squares from {0, 1, 4, 9} (about a quarter of the rows get the weight zero)."""
     return SQUARES[np.random.default_rng(seed).integers(0, 4, n)]
-
-
-def i64(a):
-    """Integer-valued binary64 data as int64 (checked)."""
-    a = np.asarray(a)
-    out = a.astype(np.int64)
-    assert np.array_equal(out, a)
-    return out
-
-
-def imatmul(A, B):
-    """int64 A @ B with both operands contiguous (numpy's integer product crawls on a transposed view)."""
-    return np.ascontiguousarray(A) @ np.ascontiguousarray(B)
 
 
 def poisoned(Mh, ncols):
