@@ -524,6 +524,23 @@ int lfpsqp_projcg_diags(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, doub
 int lfpsqp_diags_mul(lfpsqp_ctx* ctx, double a0, const lfpsqp_vec* dg, const lfpsqp_mat* off, int64_t K, const int64_t* dist, const lfpsqp_vec* v,
                      lfpsqp_vec* out);
 
+/* ... and for a WIDE grid stencil: the operator of lfpsqp_projcg_diags with K = 1 .. LFPSQP_STENCIL_MAX_DIAGS off-diagonals -- the 27-point stencil
+ * of a 3-D field (13 distances: {1, nx-1, nx, nx+1} and nx ny + {-nx-1, -nx, -nx+1, -1, 0, 1, nx-1, nx, nx+1}), and PERIODIC axes: a
+ * wrap-around edge between rows i < j is one more entry on the off-diagonal at distance j - i, so the periodic 5-point stencil has the 4
+ * distances {1, nx-1, nx, (ny-1) nx}, the periodic 7-point one 6 and the periodic 9-point one 10.  Argument lists, dist, off, the ignored
+ * entries, Av, the basis shapes, the flags (START_GIVEN honoured), the stacked form and the refusals are those of lfpsqp_projcg_diags, with
+ * LFPSQP_ERR_ARG for K outside 1 .. 13.  The scheme is the same too: ONE pass over U per iteration, two vector kernels before it (with K = 13
+ * the gather reads 26 couplings and 26 neighbours per row), and K + 1 or K + 2 weighted Gram passes per solve for U'A U, summed in the order
+ * k = 1 .. K, + cpos, - cneg.  For K <= 4 the call runs the kernels of lfpsqp_projcg_diags and returns its bits; more than four distances
+ * run the same kernels instantiated for a descriptor of 13 distances.
+ * lfpsqp_stencil_mul: out = A v (out != v), the operator on its own; the stacked pair as for lfpsqp_diags_mul. */
+#define LFPSQP_STENCIL_MAX_DIAGS 13
+int lfpsqp_projcg_stencil(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, double a0, const lfpsqp_vec* dg, const lfpsqp_mat* off, int64_t K,
+                          const int64_t* dist, lfpsqp_vec* Av, const lfpsqp_basis* U, const lfpsqp_vec* b, const lfpsqp_vec* c, double tol,
+                          int64_t maxit, int64_t n_global, int flags, const lfpsqp_projcg_work* work, int64_t* iters, double* nr);
+int lfpsqp_stencil_mul(lfpsqp_ctx* ctx, double a0, const lfpsqp_vec* dg, const lfpsqp_mat* off, int64_t K, const int64_t* dist, const lfpsqp_vec* v,
+                       lfpsqp_vec* out);
+
 /* The same solver for a GENERAL symmetric operator A -- the reference's LinearMap closure around hess_lag_vec! /
  * augmented_hess_lag_vec! (src/optimize.jl:228-230, applied at src/projcg.jl:57,74,116): `A(user, src, dest)` must produce
  * dest = A * src for device vectors of length(b) (stacked [x | gap | y] when U is a stacked basis), return 0, and leave

@@ -245,6 +245,10 @@ c_projcg_diags(ctx, x, lam, a0, dg, off, K, dist, Av, U, b, c, tol, maxit, nglob
     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Cvoid}, Ref{CBasis}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Int64, Int64, Cint, Ref{CWork}, Ref{Int64}, Ref{Float64}),
     ctx, x, lam, a0, dg, off, K, dist, Av, U, b, c, tol, maxit, nglob, flags, work, iters, nr)
 c_diags_mul(ctx, a0, dg, off, K, dist, v, out) = ccall((:lfpsqp_diags_mul, lib), Cint, (Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Cvoid}, Ptr{Cvoid}), ctx, a0, dg, off, K, dist, v, out)
+c_projcg_stencil(ctx, x, lam, a0, dg, off, K, dist, Av, U, b, c, tol, maxit, nglob, flags, work, iters, nr) = ccall((:lfpsqp_projcg_stencil, lib), Cint,
+    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Cvoid}, Ref{CBasis}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Int64, Int64, Cint, Ref{CWork}, Ref{Int64}, Ref{Float64}),
+    ctx, x, lam, a0, dg, off, K, dist, Av, U, b, c, tol, maxit, nglob, flags, work, iters, nr)
+c_stencil_mul(ctx, a0, dg, off, K, dist, v, out) = ccall((:lfpsqp_stencil_mul, lib), Cint, (Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Cvoid}, Ptr{Cvoid}), ctx, a0, dg, off, K, dist, v, out)
 c_projcg_op(ctx, x, lam, A, user, Av, U, b, c, tol, maxit, nglob, flags, work, iters, nr) = ccall((:lfpsqp_projcg_op, lib), Cint,
     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{CBasis}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Int64, Int64, Cint, Ref{CWork}, Ref{Int64}, Ref{Float64}),
     ctx, x, lam, A, user, Av, U, b, c, tol, maxit, nglob, flags, work, iters, nr)
@@ -616,10 +620,11 @@ function LinearAlgebra.mul!(dest::DeviceVector, A::BandedOperator, v::DeviceVect
     return dest
 end
 
-# (A v)_i = (a0 + dg_i) v_i + Σ_k (off_k[i-s_k] v_{i-s_k} + off_k[i] v_{i+s_k}) for 1 <= K <= 4 off-diagonals at ARBITRARY distances
-# dists = [s_1 < ... < s_K]: the stencil of a 2-D / 3-D grid in row-major order ([1, nx], [1, nx, nx*ny], [1, nx-1, nx, nx+1]).  off: an
-# n x (>= K) device matrix, column k = off_k (entries with i + s_k > n are ignored; the ends of a grid line are zeros in the data).  projcg! keeps
-# ONE pass over the basis per iteration with it (lfpsqp_projcg_diags); mul! is the LinearMap's action.
+# (A v)_i = (a0 + dg_i) v_i + Σ_k (off_k[i-s_k] v_{i-s_k} + off_k[i] v_{i+s_k}) for 1 <= K <= 13 off-diagonals at ARBITRARY distances
+# dists = [s_1 < ... < s_K]: the stencil of a 2-D / 3-D grid in row-major order ([1, nx], [1, nx, nx*ny], [1, nx-1, nx, nx+1]; 13 distances for
+# the 27-point stencil; a periodic axis adds its wrap-around edges as further distances).  off: an n x (>= K) device matrix, column k = off_k
+# (entries with i + s_k > n are ignored; the ends of a grid line are zeros in the data).  projcg! keeps ONE pass over the basis per iteration with
+# it (lfpsqp_projcg_diags for K <= 4, lfpsqp_projcg_stencil for 5 .. 13); mul! is the LinearMap's action.
 struct DiagonalsOperator
     a0::Float64
     dg::Union{Nothing,DeviceVector}
@@ -627,7 +632,8 @@ struct DiagonalsOperator
     dists::Vector{Int64}
 end
 function LinearAlgebra.mul!(dest::DeviceVector, A::DiagonalsOperator, v::DeviceVector)
-    GC.@preserve A check(dest.ctx, c_diags_mul(dest.ctx.h, A.a0, A.dg === nothing ? C_NULL : A.dg.h, A.off.h, Int64(length(A.dists)), pointer(A.dists), v.h, dest.h))
+    mul = length(A.dists) <= 4 ? c_diags_mul : c_stencil_mul
+    GC.@preserve A check(dest.ctx, mul(dest.ctx.h, A.a0, A.dg === nothing ? C_NULL : A.dg.h, A.off.h, Int64(length(A.dists)), pointer(A.dists), v.h, dest.h))
     return dest
 end
 
@@ -792,9 +798,10 @@ function projcg!(x::DeviceVector, λ::Union{Nothing,DeviceVector}, A::DiagonalsO
                  Av::DeviceVector=DeviceVector(x.ctx, length(b)), start_given::Bool=false)
     iters = Ref{Int64}(0); nr = Ref{Float64}(0.0)
     flags = (λ === nothing ? Cint(0) : LFPSQP_PROJCG_WANT_LAMBDA) | (start_given ? LFPSQP_PROJCG_START_GIVEN : Cint(0))
-    rc = GC.@preserve U A c_projcg_diags(x.ctx.h, x.h, λ === nothing ? C_NULL : λ.h, A.a0, A.dg === nothing ? C_NULL : A.dg.h, A.off.h,
-                                         Int64(length(A.dists)), pointer(A.dists), Av.h, Ref(cbasis(U)), b.h, c === nothing ? C_NULL : c.h, tol,
-                                         Int64(maxit), Int64(n_global), flags, Ref(cwork(work)), iters, nr)
+    solve = length(A.dists) <= 4 ? c_projcg_diags : c_projcg_stencil
+    rc = GC.@preserve U A solve(x.ctx.h, x.h, λ === nothing ? C_NULL : λ.h, A.a0, A.dg === nothing ? C_NULL : A.dg.h, A.off.h,
+                                Int64(length(A.dists)), pointer(A.dists), Av.h, Ref(cbasis(U)), b.h, c === nothing ? C_NULL : c.h, tol,
+                                Int64(maxit), Int64(n_global), flags, Ref(cwork(work)), iters, nr)
     if rc == LFPSQP_ERR_UNSUPPORTED && !start_given
         return projcg!(x, λ, (dest, src) -> mul!(dest, A, src), U, b, c; tol=tol, maxit=maxit, work=work, n_global=n_global)
     end

@@ -349,12 +349,17 @@ struct TriPrepSF {
     }
 };
 
-// A = a0*I + diag(dg) + K (1 .. 4) off-diagonals at RUN-TIME distances 1 <= s_1 < ... < s_K < nc -- the stencil of a 2-D / 3-D grid stored in
-// row-major order ({1, nx}, {1, nx, nx ny}, {1, nx - 1, nx, nx + 1}); lfpsqp_projcg_diags / lfpsqp_diags_mul:
+// A = a0*I + diag(dg) + K (1 .. C) off-diagonals at RUN-TIME distances 1 <= s_1 < ... < s_K < nc -- the stencil of a 2-D / 3-D grid stored in
+// row-major order ({1, nx}, {1, nx, nx ny}, {1, nx - 1, nx, nx + 1}; 13 distances for the 27-point stencil; a periodic axis adds its wrap-around
+// edges as further distances); lfpsqp_projcg_diags / lfpsqp_diags_mul (C = 4), lfpsqp_projcg_stencil / lfpsqp_stencil_mul (K > 4: C = 13):
 //     (A v)_i = (a0 + dg_i) v_i + sum_k ( off_k[i - s_k] v_{i - s_k} + off_k[i] v_{i + s_k} )
 // (off_k[i] couples rows i and i + s_k; entries with i + s_k >= nc are ignored).  Stacked vectors as for BandD: couplings on the first nc rows.
 // The neighbours are plain gathers: within a wave they are as coalesced as the rows themselves; whether they come from the L2 (near
 // distances) or from further away (a grid line or plane apart) is the memory system's business, not the kernel's.
+// C, the capacity, is a compile-time parameter: the descriptor travels as a kernel argument and its size is that of its distances; the loops over
+// them are bounded by C (unrolled at C = 4; at C = 13 the compiler keeps the loop).
+constexpr int kDiagsNarrow = 4, kDiagsWide = LFPSQP_STENCIL_MAX_DIAGS;
+template <int C>
 struct DiagsD {
     double a0;
     const double* dg;
@@ -363,13 +368,13 @@ struct DiagsD {
     int64_t n;
     int64_t nc;
     int K;
-    int64_t s[4];
+    int64_t s[C];
     __device__ __forceinline__ const double* col(int k) const { return off + (int64_t)k * ldo; }
     // row j < nc of the off-diagonal part applied to the vector whose entry r is src(r): per distance the lower, then the upper coupling
     template <class SRC>
     __device__ __forceinline__ double couple(int64_t j, double o, SRC&& src) const {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
+        for (int k = 0; k < C; ++k) {
             if (k >= K) break;
             const double* ok = col(k);
             const int64_t sk = s[k];
@@ -379,8 +384,9 @@ struct DiagsD {
         return o;
     }
 };
+template <int C>
 struct DiagsMulF {   // out = A v
-    DiagsD A;
+    DiagsD<C> A;
     const double* v;
     double* out;
     const int64_t* istat;     // nullptr: always; else only while the solve is running
@@ -403,8 +409,9 @@ struct DiagsMulF {   // out = A v
 // (DiagsMulF, while the solve runs) and this kernel gathers  q_i = sum_k (off_k[i-s_k] rr_{i-s_k} + off_k[i] rr_{i+s_k})  from
 // rr = g + alpha ad at the shifted rows (the same fma as the pass forms for its own row).  ad == nullptr: rr = g as stored -- the initial
 // residual (INIT), or the projected residual ux that DiagsPrepSF left for a stacked basis.
+template <int C>
 struct DiagsGatherF {
-    DiagsD A;                 // n = nc = the rows with couplings
+    DiagsD<C> A;              // n = nc = the rows with couplings
     const double* g;
     const double* ad;
     double* q;
@@ -431,9 +438,9 @@ struct DiagsGatherF {
 // Stacked basis (PcgFuseTri<true, .>), the row-local half of TriPrepSF:  ad = (T d)_x  and the x half of the residual projected off the diagonal
 // block,  ux_r = rx_r - Dx_r (Dx_r rx_r + Dy_r ry_r)  with  rr = g + alpha A d  (the pass's own expressions), stored once so that DiagsGatherF can
 // gather it at the far rows.  INIT: rr is the stored initial residual, only ux is written.
-template <bool INIT>
+template <int C, bool INIT>
 struct DiagsPrepSF {
-    DiagsD A;                 // n = nc = N; dg stacked (the y half at dg + hs)
+    DiagsD<C> A;              // n = nc = N; dg stacked (the y half at dg + hs)
     int64_t hs;
     const double *Dx, *Dy;
     const double* g;
@@ -1379,7 +1386,8 @@ int lfpsqp_factored_basis_supported(const lfpsqp_ctx* ctx, const lfpsqp_mat* A, 
 // negative part costs one more pass (the normal case for second differences, interior stencil kappa [1, -4, 6, -4, 1]).  The passes are summed
 // in the order k = 1 .. B, + cpos, - cneg.
 // One kernel pair for the whole family: a band of width B is the descriptor with K = B and s = {1 .. B} (BandD::col(k) = DiagsD::col(k - 1)).
-__global__ __launch_bounds__(256) void diags_weights_kernel(DiagsD A, double* __restrict__ wabs /* K columns, npad apart */, double* __restrict__ sgn,
+template <int C>
+__global__ __launch_bounds__(256) void diags_weights_kernel(DiagsD<C> A, double* __restrict__ wabs /* K columns, npad apart */, double* __restrict__ sgn,
                                                             double* __restrict__ cpos, double* __restrict__ cneg, int64_t npad, double* __restrict__ anyneg) {
     bool neg = false;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < npad; i += (int64_t)gridDim.x * 256) {
@@ -1407,7 +1415,8 @@ __global__ __launch_bounds__(256) void diags_weights_kernel(DiagsD A, double* __
 }
 // stacked basis: the reduced operator Q_Z'A Q_Z = Z' At Z of At = S_x T S_x + S_y diag(ay) S_y (PcgFuseTri<true, .>) -- the same Gram passes as
 // above, over At instead of A:  At_ii = sx_i^2 ax_i + sy_i^2 ay_i,  At_{i,i+s_k} = sx_i off_k[i] sx_{i+s_k}
-__global__ __launch_bounds__(256) void diags_stack_weights_kernel(DiagsD A, int64_t hs, const double* __restrict__ sx, const double* __restrict__ sy,
+template <int C>
+__global__ __launch_bounds__(256) void diags_stack_weights_kernel(DiagsD<C> A, int64_t hs, const double* __restrict__ sx, const double* __restrict__ sy,
                                                                   double* __restrict__ adg, double* __restrict__ aoff /* K columns, npad apart */, int64_t npad) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < npad; i += (int64_t)gridDim.x * 256) {
         double dv = 0.0;
@@ -1495,19 +1504,20 @@ static int reduced_from_weights(lfpsqp_ctx* ctx, const lfpsqp_mat* Z, int mc, in
 }
 // Mh (m x m, column-major, host) = U'A U for U = Z[:, :mc] (W == nullptr, m == mc) or U = Z[:, :mc] W (W: mc x m, host); sk: a stacked basis,
 // U = [sx; sy] .* (that), and A over the x half (A0.n = A0.nc = N, the rows of Z; dg stacked)
-static int reduced_operator(lfpsqp_ctx* ctx, const lfpsqp_mat* Z, int mc, const DiagsD& A0, const double* W, int m, std::vector<double>& Mh,
+template <int C>
+static int reduced_operator(lfpsqp_ctx* ctx, const lfpsqp_mat* Z, int mc, const DiagsD<C>& A0, const double* W, int m, std::vector<double>& Mh,
                             const StackD* sk = nullptr) {
     const int64_t n = A0.n;
     TriWeights w;
     LF_TRY(tri_weights_alloc(ctx, n, A0.K, sk != nullptr, w));
-    DiagsD A = A0;
+    DiagsD<C> A = A0;
     if (sk) {
-        hipLaunchKernelGGL(diags_stack_weights_kernel, dim3(w.nblk), dim3(256), 0, ctx->stream, A0, sk->hs, sk->sx, sk->sy, w.adg, w.aoff, w.npad);
+        hipLaunchKernelGGL(diags_stack_weights_kernel<C>, dim3(w.nblk), dim3(256), 0, ctx->stream, A0, sk->hs, sk->sx, sk->sy, w.adg, w.aoff, w.npad);
         LF_LAUNCH_CHECK(ctx);
         A.a0 = 0.0; A.dg = w.adg; A.off = w.aoff; A.ldo = w.npad;
     }
     LF_HIP(ctx, hipMemsetAsync(w.anyneg, 0, sizeof(double), ctx->stream));
-    hipLaunchKernelGGL(diags_weights_kernel, dim3(w.nblk), dim3(256), 0, ctx->stream, A, w.wabs, w.sgn, w.cpos, w.cneg, w.npad, w.anyneg);
+    hipLaunchKernelGGL(diags_weights_kernel<C>, dim3(w.nblk), dim3(256), 0, ctx->stream, A, w.wabs, w.sgn, w.cpos, w.cneg, w.npad, w.anyneg);
     LF_LAUNCH_CHECK(ctx);
     return reduced_from_weights(ctx, Z, mc, n, A0.K, A0.s, w, W, m, Mh);
 }
@@ -1515,7 +1525,8 @@ static int reduced_operator(lfpsqp_ctx* ctx, const lfpsqp_mat* Z, int mc, const 
 // A coupled operator as its entry point describes it: K coupling columns of `rows` entries, ld apart, next to the diagonal (a0, dg).
 //   BAND   column k couples rows i and i + k + 1, K = the bandwidth (1 .. 4) is a compile-time parameter of the kernels (BandD<K>, register
 //          windows): lfpsqp_projcg_tridiag (K = 1, off a vector), lfpsqp_projcg_band (off a plain matrix) and their _mul;
-//   DIAGS  column k couples rows i and i + dist[k], run-time distances (DiagsD, gathers): lfpsqp_projcg_diags, lfpsqp_diags_mul.
+//   DIAGS  column k couples rows i and i + dist[k], run-time distances (DiagsD, gathers): lfpsqp_projcg_diags, lfpsqp_diags_mul (K <= 4) and
+//          lfpsqp_projcg_stencil, lfpsqp_stencil_mul (K <= 13; more than four distances run the kernels of the wide descriptor).
 struct CoupledOp {
     enum Kind { BAND, DIAGS } kind;
     const char* who;          // the entry point, for messages
@@ -1524,16 +1535,27 @@ struct CoupledOp {
     const double* off;
     int64_t ld, rows;
     int K;
-    int64_t dist[4];          // BAND: {1, 2, 3, 4}
+    int64_t dist[kDiagsWide]; // BAND: {1, 2, 3, 4}
     const double* dgp() const { return dg ? dg->p : nullptr; }
     // over vectors of n rows, couplings on the first nc
-    DiagsD diags(int64_t n, int64_t nc) const { return DiagsD{a0, dgp(), off, ld, n, nc, K, {dist[0], dist[1], dist[2], dist[3]}}; }
+    template <int C>
+    DiagsD<C> diags(int64_t n, int64_t nc) const {
+        DiagsD<C> A{a0, dgp(), off, ld, n, nc, K, {}};
+        for (int k = 0; k < C; ++k) A.s[k] = dist[k];
+        return A;
+    }
+    bool wide() const { return K > kDiagsNarrow; }
     template <int B>
     BandD<B> band(int64_t n, int64_t nc) const { return BandD<B>{a0, dgp(), off, ld, n, nc}; }
     static CoupledOp banded(const char* who, double a0, const lfpsqp_vec* dg, const double* off, int64_t ld, int64_t rows, int bw) {
         return CoupledOp{BAND, who, a0, dg, off, ld, rows, bw, {1, 2, 3, 4}};
     }
 };
+// fn(std::integral_constant<int, C>) for the descriptor's capacity: the narrow one wherever it holds the distances
+template <typename F>
+static int with_diags(const CoupledOp& A, F&& fn) {
+    return A.wide() ? fn(std::integral_constant<int, kDiagsWide>{}) : fn(std::integral_constant<int, kDiagsNarrow>{});
+}
 // fn(std::integral_constant<int, B>) for B = bw (1 .. 4)
 template <typename F>
 static int with_band(int bw, F&& fn) {
@@ -1547,7 +1569,11 @@ static int with_band(int bw, F&& fn) {
 
 // out = A v over vectors of n rows, couplings on the first nc
 static int coupled_mul(lfpsqp_ctx* ctx, const CoupledOp& A, int64_t n, int64_t nc, const double* v, double* out) {
-    if (A.kind == CoupledOp::DIAGS) return run_vec<DiagsMulF, 0, NoPost>(ctx, n, DiagsMulF{A.diags(n, nc), v, out, nullptr}, 0u, nullptr, NoPost());
+    if (A.kind == CoupledOp::DIAGS)
+        return with_diags(A, [&](auto Cc) -> int {
+            constexpr int C = decltype(Cc)::value;
+            return run_vec<DiagsMulF<C>, 0, NoPost>(ctx, n, DiagsMulF<C>{A.template diags<C>(n, nc), v, out, nullptr}, 0u, nullptr, NoPost());
+        });
     return with_band(A.K, [&](auto Bc) -> int {
         constexpr int B = decltype(Bc)::value;
         return run_vec<TriMulF<B>, 0, NoPost>(ctx, n, TriMulF<B>{A.template band<B>(n, nc), v, out, nullptr}, 0u, nullptr, NoPost());
@@ -1684,12 +1710,14 @@ static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const
     std::vector<double> triMh;
     if (cop) {
         // (stacked: dg over both halves, off the x half's couplings -- N rows; the y half is diagonal)
-        LF_ARG(ctx, cop->off && cop->rows == N && cop->K >= 1 && cop->K <= 4 && (!cop->dg || cop->dg->n == nv));
+        LF_ARG(ctx, cop->off && cop->rows == N && cop->K >= 1 && cop->K <= (cop->kind == CoupledOp::DIAGS ? kDiagsWide : kDiagsNarrow) && (!cop->dg || cop->dg->n == nv));
         if (!fused || !plain_mat(Z) || ctx->comm_active())
             return set_err(ctx, LFPSQP_ERR_UNSUPPORTED, "%s: needs the one-pass iteration over a dense basis (4 .. 1024 columns, no matrix "
                                                         "view) on a single rank (the couplings would cross the shard boundaries); use lfpsqp_projcg_op",
                            cop->who);
-        LF_TRY(reduced_operator(ctx, Z, mc, cop->diags(N, N), DF ? U->W : nullptr, m, triMh, stacked ? &sk : nullptr));
+        LF_TRY(with_diags(*cop, [&](auto Cc) -> int {
+            return reduced_operator(ctx, Z, mc, cop->template diags<decltype(Cc)::value>(N, N), DF ? U->W : nullptr, m, triMh, stacked ? &sk : nullptr);
+        }));
     }
     double* dTriM = nullptr;
     double *lrUtV = nullptr, *lrSig = nullptr, *lrVdraw = nullptr, *lrVdc = nullptr, *lrVtv = nullptr;
@@ -1811,15 +1839,18 @@ static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const
             });
         // run-time distances: A d stored first, then the gather of the neighbours' rr (stacked: of ux, kept in the set-up's scratch, which is
         // free once M is on the device)
-        const DiagsD Ab = cop->diags(N, N);
-        if constexpr (ST) {
-            double* ux = ctx->d_tri;
-            LF_TRY((run_vec<DiagsPrepSF<INIT>, 0, NoPost>(ctx, N, DiagsPrepSF<INIT>{Ab, hs, sk.Dx, sk.Dy, src, dsrc, ad, ux, scal, istat}, 0u, nullptr, NoPost())));
-            return run_vec<DiagsGatherF, 0, NoPost>(ctx, N, DiagsGatherF{Ab, ux, nullptr, q, scal, istat}, 0u, nullptr, NoPost());
-        } else {
-            if constexpr (!INIT) LF_TRY((run_vec<DiagsMulF, 0, NoPost>(ctx, N, DiagsMulF{Ab, dsrc, ad, istat}, 0u, nullptr, NoPost())));
-            return run_vec<DiagsGatherF, 0, NoPost>(ctx, N, DiagsGatherF{Ab, src, ad, q, scal, istat}, 0u, nullptr, NoPost());
-        }
+        return with_diags(*cop, [&](auto Cc) -> int {
+            constexpr int C = decltype(Cc)::value;
+            const DiagsD<C> Ab = cop->template diags<C>(N, N);
+            if constexpr (ST) {
+                double* ux = ctx->d_tri;
+                LF_TRY((run_vec<DiagsPrepSF<C, INIT>, 0, NoPost>(ctx, N, DiagsPrepSF<C, INIT>{Ab, hs, sk.Dx, sk.Dy, src, dsrc, ad, ux, scal, istat}, 0u, nullptr, NoPost())));
+                return run_vec<DiagsGatherF<C>, 0, NoPost>(ctx, N, DiagsGatherF<C>{Ab, ux, nullptr, q, scal, istat}, 0u, nullptr, NoPost());
+            } else {
+                if constexpr (!INIT) LF_TRY((run_vec<DiagsMulF<C>, 0, NoPost>(ctx, N, DiagsMulF<C>{Ab, dsrc, ad, istat}, 0u, nullptr, NoPost())));
+                return run_vec<DiagsGatherF<C>, 0, NoPost>(ctx, N, DiagsGatherF<C>{Ab, src, ad, q, scal, istat}, 0u, nullptr, NoPost());
+            }
+        });
     };
     auto launch_fused = [&](int init) -> int {
         const int slot = init ? -1 : 3;
@@ -2092,11 +2123,12 @@ extern "C" int lfpsqp_band_mul(lfpsqp_ctx* ctx, double a0, const lfpsqp_vec* dg,
     return coupled_mul_entry(ctx, CoupledOp::banded("lfpsqp_band_mul", a0, dg, off->p, off->ld, off->n, (int)bw), v, out);
 }
 
-// the off-diagonals of lfpsqp_projcg_diags / lfpsqp_diags_mul: K (1 .. 4) columns of a plain matrix, strictly increasing distances in 1 .. rows - 1
+// the off-diagonals of lfpsqp_projcg_diags / lfpsqp_diags_mul (Kmax = 4) and of lfpsqp_projcg_stencil / lfpsqp_stencil_mul (Kmax = 13): K (1 .. Kmax)
+// columns of a plain matrix, strictly increasing distances in 1 .. rows - 1
 static int diags_op(lfpsqp_ctx* ctx, const char* who, double a0, const lfpsqp_vec* dg, const lfpsqp_mat* off, int64_t K, const int64_t* dist,
-                    CoupledOp& A) {
-    LF_ARG(ctx, off && plain_mat(off) && dist && K >= 1 && K <= 4 && off->m >= K);
-    A = CoupledOp{CoupledOp::DIAGS, who, a0, dg, off->p, off->ld, off->n, (int)K, {0, 0, 0, 0}};
+                    int Kmax, CoupledOp& A) {
+    LF_ARG(ctx, off && plain_mat(off) && dist && K >= 1 && K <= Kmax && off->m >= K);
+    A = CoupledOp{CoupledOp::DIAGS, who, a0, dg, off->p, off->ld, off->n, (int)K, {}};
     for (int k = 0; k < K; ++k) {
         LF_ARG(ctx, dist[k] >= 1 && dist[k] < off->n && (k == 0 || dist[k] > dist[k - 1]));
         A.dist[k] = dist[k];
@@ -2110,7 +2142,7 @@ extern "C" int lfpsqp_projcg_diags(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* l
     LF_RANGE("lfpsqp_projcg_diags");
     LF_ARG(ctx, ctx && Av);
     CoupledOp A;
-    LF_TRY(diags_op(ctx, "lfpsqp_projcg_diags", a0, dg, off, K, dist, A));
+    LF_TRY(diags_op(ctx, "lfpsqp_projcg_diags", a0, dg, off, K, dist, kDiagsNarrow, A));
     return projcg_coupled(ctx, x, lambda, A, Av, U, b, c, tol, maxit, n_global, flags, work, iters, nr);
 }
 
@@ -2118,7 +2150,25 @@ extern "C" int lfpsqp_diags_mul(lfpsqp_ctx* ctx, double a0, const lfpsqp_vec* dg
                                 const lfpsqp_vec* v, lfpsqp_vec* out) {
     LF_ARG(ctx, ctx);
     CoupledOp A;
-    LF_TRY(diags_op(ctx, "lfpsqp_diags_mul", a0, dg, off, K, dist, A));
+    LF_TRY(diags_op(ctx, "lfpsqp_diags_mul", a0, dg, off, K, dist, kDiagsNarrow, A));
+    return coupled_mul_entry(ctx, A, v, out);
+}
+
+extern "C" int lfpsqp_projcg_stencil(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, double a0, const lfpsqp_vec* dg, const lfpsqp_mat* off, int64_t K,
+                                     const int64_t* dist, lfpsqp_vec* Av, const lfpsqp_basis* U, const lfpsqp_vec* b, const lfpsqp_vec* c, double tol,
+                                     int64_t maxit, int64_t n_global, int flags, const lfpsqp_projcg_work* work, int64_t* iters, double* nr) {
+    LF_RANGE("lfpsqp_projcg_stencil");
+    LF_ARG(ctx, ctx && Av);
+    CoupledOp A;
+    LF_TRY(diags_op(ctx, "lfpsqp_projcg_stencil", a0, dg, off, K, dist, kDiagsWide, A));
+    return projcg_coupled(ctx, x, lambda, A, Av, U, b, c, tol, maxit, n_global, flags, work, iters, nr);
+}
+
+extern "C" int lfpsqp_stencil_mul(lfpsqp_ctx* ctx, double a0, const lfpsqp_vec* dg, const lfpsqp_mat* off, int64_t K, const int64_t* dist,
+                                  const lfpsqp_vec* v, lfpsqp_vec* out) {
+    LF_ARG(ctx, ctx);
+    CoupledOp A;
+    LF_TRY(diags_op(ctx, "lfpsqp_stencil_mul", a0, dg, off, K, dist, kDiagsWide, A));
     return coupled_mul_entry(ctx, A, v, out);
 }
 

@@ -253,14 +253,75 @@ class ChainSeparableLinear(SeparableLinearBallBox):
         axpby(1.0, self._deg, 1.0, hx)
 
 
-def grid_laplacian(shape, kappa: float = 1.0):
+def graph_diagonals(n: int, i, j, w):
+    """The weighted graph Laplacian of an edge list as the arrays of a :class:`DiagonalsOperator`: for edges (i_e, j_e), i_e < j_e < n, with weights
+    w_e (a scalar or one per edge) -- the Hessian of 1/2 sum_e w_e (x_i - x_j)^2 -- returns ``(diag, off, dists)``: ``diag[i] += w``, ``diag[j] += w``
+    and ``off[i, column of distance j - i] -= w`` per edge, ``dists`` the distinct distances j - i in increasing order, ``off`` n x K in Fortran
+    order with zeros wherever no edge put a value (the ignored tails i + s_k >= n among them).  Repeated edges add up.  More than 13 distinct
+    distances do not fit one operator: ValueError."""
+    n = int(n)
+    i, j = np.asarray(i, dtype=np.int64).ravel(), np.asarray(j, dtype=np.int64).ravel()
+    w = np.broadcast_to(np.asarray(w, dtype=float), i.shape)
+    assert i.shape == j.shape and i.size >= 1, "graph_diagonals: at least one edge"
+    assert np.all((0 <= i) & (i < j) & (j < n)), "graph_diagonals: edges (i, j) with 0 <= i < j < n"
+    d = j - i
+    dists = np.flatnonzero(np.bincount(d, minlength=2))                # (counting, not sorting: the edge list of a 1e7-point volume has 1.3e8 entries)
+    if len(dists) > 13:
+        raise ValueError(f"graph_diagonals: {len(dists)} distinct distances j - i, at most 13 off-diagonals fit one operator")
+    diag = np.bincount(i, w, n) + np.bincount(j, w, n)
+    off = 0.0 - np.bincount(i + np.searchsorted(dists, d) * n, w, n * len(dists)).reshape((n, len(dists)), order='F')
+    return diag, off, tuple(int(s) for s in dists)
+
+
+def _grid_edges(shape, periodic, corners):
+    """(i, j), i < j: the edges of the grid graph in row-major numbering.  Every offset in {-1, 0, 1}^d (corners) or along one axis whose first
+    nonzero component is +1 names each edge once; a periodic axis wraps, any other drops the neighbours beyond its end."""
+    import itertools
+    d = len(shape)
+    if corners:
+        offsets = [o for o in itertools.product((-1, 0, 1), repeat=d) if next((c for c in o if c), 0) > 0]
+    else:
+        offsets = [tuple(int(ax == k) for k in range(d)) for ax in range(d)]
+    coords = np.indices(shape).reshape(d, -1)
+    flat = np.arange(coords.shape[1])
+    ii, jj = [], []
+    for o in offsets:
+        keep = np.ones(len(flat), dtype=bool)
+        nb = []
+        for ax in range(d):
+            c = coords[ax] + o[ax]
+            if periodic[ax]:
+                c = c % shape[ax]
+            else:
+                keep &= (c >= 0) & (c < shape[ax])
+            nb.append(c)
+        if not keep.any():
+            continue
+        q = np.ravel_multi_index([c[keep] for c in nb], shape)
+        ii.append(np.minimum(flat[keep], q))
+        jj.append(np.maximum(flat[keep], q))
+    return np.concatenate(ii), np.concatenate(jj)
+
+
+def grid_laplacian(shape, kappa: float = 1.0, periodic=False, corners: bool = False):
     """kappa L for the grid graph of a 2-D or 3-D field stored in row-major order (last axis fastest), L = D - W its Laplacian (edges between
     neighbours along each axis): returns ``(diag, off, dists)`` -- the diagonal kappa deg_i (length n = prod(shape)), the couplings (n x K,
     column k: entry i couples points i and i + dists[k]; -kappa on an edge, 0 where i is the last point along that axis) and the distances
-    (1, n_last, n_last n_mid ...) in increasing order; axes of length 1 have no edges and no column."""
+    (1, n_last, n_last n_mid ...) in increasing order; axes of length 1 have no edges and no column.
+    ``periodic`` (a bool, or one per axis): the axis closes on itself -- its wrap-around edge between rows i < j is one more entry at distance
+    j - i (2-D: distances (1, nx - 1, nx, (ny - 1) nx)); the axis needs at least 3 points (with 2 the wrap would repeat the one edge).
+    ``corners``: every pair of points whose indices differ by at most 1 along every axis is an edge of weight kappa -- 8 neighbours in 2-D
+    (4 distances), 26 in 3-D (13).  Both variants are built through :func:`graph_diagonals`, which raises ValueError where more than 13 distances
+    arise (a periodic 3-D grid with corners)."""
     shape = tuple(int(s) for s in shape)
     assert len(shape) in (2, 3) and all(s >= 1 for s in shape)
     n = int(np.prod(shape))
+    per = (bool(periodic),) * len(shape) if np.ndim(periodic) == 0 else tuple(bool(p) for p in periodic)
+    assert len(per) == len(shape), "grid_laplacian: periodic is a bool or one bool per axis"
+    if any(per) or corners:
+        assert all(s >= 3 for s, p in zip(shape, per) if p), "grid_laplacian: a periodic axis needs at least 3 points"
+        assert n > 1, "grid_laplacian: a grid of more than one point"
+        return graph_diagonals(n, *_grid_edges(shape, per, bool(corners)), float(kappa))
     idx = np.arange(n).reshape(shape)
     diag = np.zeros(n)
     cols, dists = [], []
@@ -285,10 +346,13 @@ class GridSeparableLinear(SeparableLinearBallBox):
     optional ball (slack variable) and box bounds of :class:`QuadLinearBallBox`.  The Lagrangian Hessian is a diagonal, phi''(x_i) + kappa deg_i
     (+ 2 lam_ball), plus one off-diagonal per axis FAR from the main one (distances 1, nx, nx ny: :func:`grid_laplacian`): ``diagonals`` =
     (dists, off) below, and ``optimize`` hands it to projcg_ as a :class:`DiagonalsOperator` -- the truncated-Newton solves keep one pass over
-    the basis per iteration (lfpsqp_projcg_diags; with bounds the augmented stacked diagonal next to the same couplings).  The slack row, when
-    the ball is there, has no couplings.  One rank (the couplings would cross the shard boundaries)."""
+    the basis per iteration (lfpsqp_projcg_diags; with bounds the augmented stacked diagonal next to the same couplings).  ``periodic`` and
+    ``corners`` are those of :func:`grid_laplacian`: a torus, and the 9- / 27-point neighbourhood (up to 13 off-diagonals:
+    lfpsqp_projcg_stencil).  The slack row, when the ball is there, has no couplings.  One rank (the couplings would cross the shard
+    boundaries)."""
 
-    def __init__(self, ctx: Context, shape, m: int, Jct: DeviceMatrix, b, kind: int, a, c=0.0, kappa: float = 1.0, **kw):
+    def __init__(self, ctx: Context, shape, m: int, Jct: DeviceMatrix, b, kind: int, a, c=0.0, kappa: float = 1.0, periodic=False,
+                 corners: bool = False, **kw):
         n = int(np.prod(shape))
         assert kw.get("n_global", n) in (None, n), "grid objective: one rank (the couplings would cross the shard boundaries)"
         super().__init__(ctx, n, m, Jct, b, kind, a, c, **kw)
@@ -296,7 +360,7 @@ class GridSeparableLinear(SeparableLinearBallBox):
         self.shape = tuple(int(s) for s in shape)
         self.kappa = float(kappa)
         N = self.N                                                        # n, or n + 1 with the ball's slack variable (no coupling to it)
-        deg_h, off_h, dists = grid_laplacian(self.shape, self.kappa)
+        deg_h, off_h, dists = grid_laplacian(self.shape, self.kappa, periodic, corners)
         deg = np.zeros(N)
         off = np.zeros((N, len(dists)), order='F')
         deg[:n], off[:n] = deg_h, off_h

@@ -168,25 +168,40 @@ class BandedOperator(_CoupledOperator):
 
 
 class DiagonalsOperator(_CoupledOperator):
-    """(A v)_i = (a0 + dg_i) v_i + sum_k (off_k[i - s_k] v_{i - s_k} + off_k[i] v_{i + s_k}) for 1 <= K <= 4 off-diagonals at ARBITRARY distances
+    """(A v)_i = (a0 + dg_i) v_i + sum_k (off_k[i - s_k] v_{i - s_k} + off_k[i] v_{i + s_k}) for 1 <= K <= 13 off-diagonals at ARBITRARY distances
     ``dists`` = (s_1 < ... < s_K): the Hessian of a smoothness / diffusion term on a 2-D or 3-D field in row-major order ((1, nx), (1, nx, nx ny),
-    (1, nx - 1, nx, nx + 1) for the 5-, 7- and 9-point stencils; :func:`lfpsqp_jl_amd.problems.grid_laplacian`).  ``off``: DeviceMatrix with n
-    rows and at least K columns, column k-1 = off_k (entry i couples rows i and i + s_k; entries with i + s_k >= n are ignored; the ends of a
-    grid line are zeros in the data).  On a :class:`DeviceBasis` projcg_ runs it on the fused ONE-pass iteration (lfpsqp_projcg_diags);
-    ``mul_`` is the operator on its own (lfpsqp_diags_mul), which the generic loop / lfpsqp_projcg_op use -- two passes over the basis per
-    iteration.  ``fused = False`` sends projcg_ to that callback path.  With bounds (a stacked basis): ``dg`` is a :class:`StackedVector` and
-    ``off`` has N rows, the couplings of the x half, as for :class:`BandedOperator`."""
+    (1, nx - 1, nx, nx + 1) for the 5-, 7- and 9-point stencils, 13 distances for the 27-point one; a periodic axis adds its wrap-around edges as
+    further distances; :func:`lfpsqp_jl_amd.problems.grid_laplacian`, :func:`lfpsqp_jl_amd.problems.graph_diagonals`).  ``off``: DeviceMatrix with
+    n rows and at least K columns, column k-1 = off_k (entry i couples rows i and i + s_k; entries with i + s_k >= n are ignored; the ends of a
+    grid line are zeros in the data).  On a :class:`DeviceBasis` projcg_ runs it on the fused ONE-pass iteration (lfpsqp_projcg_diags for
+    K <= 4, exactly as before; lfpsqp_projcg_stencil for 5 .. 13); ``mul_`` is the operator on its own (lfpsqp_diags_mul / lfpsqp_stencil_mul),
+    which the generic loop / lfpsqp_projcg_op use -- two passes over the basis per iteration.  ``fused = False`` sends projcg_ to that callback
+    path.  More than 13 distances: ValueError.  With bounds (a stacked basis): ``dg`` is a :class:`StackedVector` and ``off`` has N rows, the
+    couplings of the x half, as for :class:`BandedOperator`.
+
+    SET-UP COST.  The one-pass solve forms U'A U first: K + 1 weighted Gram passes over the basis (K + 2 when A is not diagonally dominant), so
+    14 or 15 at K = 13, where the callback path has none.  Not measured on the MI355X yet (FINDINGS.md 18): by the figures of the narrow path (a
+    run-time-distance Gram pass 4.6-5.1 ms at (1e7, 128), about 1.2 ms gained per iteration) the break-even against ``fused = False`` lies
+    at several tens of iterations per solve at K = 13 -- for shorter solves ``fused = False`` is the better choice;
+    ``tools/time_diags.py GRID M --corners --split-callback`` measures both for a given shape."""
+
+    MAX_DIAGS = 13                                  # LFPSQP_STENCIL_MAX_DIAGS
 
     def __init__(self, a0: float, dg: DeviceVector | None, off: DeviceMatrix, dists):
         super().__init__(a0, dg, off)
         self.dists = tuple(int(s) for s in dists)
+        if len(self.dists) > self.MAX_DIAGS:
+            raise ValueError(f"DiagonalsOperator: {len(self.dists)} off-diagonals, at most {self.MAX_DIAGS}")
         self._dist_c = (_capi.c_i64 * max(len(self.dists), 1))(*self.dists)
+        self._wide = len(self.dists) > 4            # (up to four distances: the entries and kernels of the narrow descriptor)
 
     def _mul(self, ctx, v, out):
-        return ctx.L.lfpsqp_diags_mul(ctx.h, self.a0, self._dg_h(), self.off.h, len(self.dists), self._dist_c, v.h, out.h)
+        mul = ctx.L.lfpsqp_stencil_mul if self._wide else ctx.L.lfpsqp_diags_mul
+        return mul(ctx.h, self.a0, self._dg_h(), self.off.h, len(self.dists), self._dist_c, v.h, out.h)
 
     def _solve(self, ctx, head, tail):
-        return ctx.L.lfpsqp_projcg_diags(*head, self.a0, self._dg_h(), self.off.h, len(self.dists), self._dist_c, *tail)
+        solve = ctx.L.lfpsqp_projcg_stencil if self._wide else ctx.L.lfpsqp_projcg_diags
+        return solve(*head, self.a0, self._dg_h(), self.off.h, len(self.dists), self._dist_c, *tail)
 
 
 class DeviceBasis:
