@@ -541,6 +541,39 @@ int lfpsqp_projcg_stencil(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, do
 int lfpsqp_stencil_mul(lfpsqp_ctx* ctx, double a0, const lfpsqp_vec* dg, const lfpsqp_mat* off, int64_t K, const int64_t* dist, const lfpsqp_vec* v,
                        lfpsqp_vec* out);
 
+/* ... and for a SPARSE SYMMETRIC Hessian, the couplings described by ROW INDICES instead of distances: A = a0*I + diag(dg) + S with S the symmetric
+ * off-diagonal part, at most LFPSQP_SPHESS_MAX_ROW entries per row -- a smoothness term on a triangle mesh, a k-nearest-neighbour graph, a grid
+ * whose points are not numbered in row-major order, the 26-neighbour periodic 3-D stencil (42 distances): everything the distance form cannot
+ * express; the reference wraps such a hess_lag_vec! in a LinearMap (src/optimize.jl:228-230, applied at src/projcg.jl:57,74,116).
+ * lfpsqp_sphess_create builds the handle ONCE from host triplets (0-based, any order): a triplet (i, j, v), i != j, adds v to BOTH A_ij and A_ji;
+ * duplicates add up, (j, i) counting as a duplicate of (i, j); a position whose duplicates sum to zero keeps its slot.  LFPSQP_ERR_ARG: i == j (the
+ * diagonal is dg's job), an index outside [0, n), a non-finite value.  LFPSQP_ERR_UNSUPPORTED: a row with more than 32 distinct neighbours after
+ * merging (32 is accepted), n >= 2^31 (indices are stored as int32).  The values are constant over the handle's lifetime: the x-dependent part of
+ * a Lagrangian Hessian arrives through dg, as for every coupled kind.
+ * Two ELL forms on the device (slot k: one int32 index array and one double array of padded length -- consecutive rows of a slot are coalesced):
+ *   by rows (row_width = the largest row degree): a row's neighbours in increasing index order, which fixes the summation order of the products,
+ *     (A v)_i = fma chain over the row's slots in slot order, starting from (a0 + dg_i) v_i; an empty slot holds the row itself and 0.0;
+ *   by edges (edge_width): every undirected edge once, at one of its endpoints, its OWNER -- the set-up passes.  Owner rule: the edges (i, j),
+ *     i < j, are visited in lexicographic order; an edge goes to j if j owns strictly fewer edges so far, otherwise to i.  edge_width is the largest
+ *     number of edges one row owns (row_width / 2 rounded up at best).
+ * lfpsqp_projcg_sparse: still ONE pass over U per iteration, and the pass is that of lfpsqp_projcg_tridiag; before it two vector kernels store A d
+ * and gather the neighbours' part of A rr through the row form (12 bytes per stored entry), and U'A U is formed once per solve by edge_width + 1 or
+ * + 2 weighted Gram passes whose operand gathers the partner rows, summed in the order k = 0 .. edge_width - 1, + cpos, - cneg (no n x m scratch).
+ * Av, the basis shapes, the flags (START_GIVEN honoured), the stacked form (S of N rows, the x half's couplings; dg stacked) and the refusals are
+ * those of lfpsqp_projcg_band / _diags: LFPSQP_ERR_UNSUPPORTED for a matrix view as basis, fewer than 4 or more than 1024 columns, a communicator,
+ * c != 0 with a stacked basis; LFPSQP_ERR_ARG for RESUME / START_PROJECTED, S == NULL, S.n different from the couplings' rows.  Iterates, counts and
+ * exits as projcg! with A as a matrix (src/projcg.jl:40-121), to rounding; a solve is bit-reproducible per handle.
+ * lfpsqp_sphess_mul: out = A v (out != v), the operator on its own; the stacked pair as for lfpsqp_diags_mul; a communicator: LFPSQP_ERR_UNSUPPORTED. */
+typedef struct lfpsqp_sphess lfpsqp_sphess;
+#define LFPSQP_SPHESS_MAX_ROW 32
+int lfpsqp_sphess_create(lfpsqp_ctx* ctx, int64_t n, int64_t nnz, const int64_t* rows, const int64_t* cols, const double* vals, lfpsqp_sphess** out);
+int lfpsqp_sphess_free(lfpsqp_ctx* ctx, lfpsqp_sphess* S);
+int lfpsqp_sphess_info(const lfpsqp_sphess* S, int64_t* n, int64_t* nedges, int64_t* row_width, int64_t* edge_width);
+int lfpsqp_sphess_mul(lfpsqp_ctx* ctx, double a0, const lfpsqp_vec* dg, const lfpsqp_sphess* S, const lfpsqp_vec* v, lfpsqp_vec* out);
+int lfpsqp_projcg_sparse(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, double a0, const lfpsqp_vec* dg, const lfpsqp_sphess* S, lfpsqp_vec* Av,
+                         const lfpsqp_basis* U, const lfpsqp_vec* b, const lfpsqp_vec* c, double tol, int64_t maxit, int64_t n_global, int flags,
+                         const lfpsqp_projcg_work* work, int64_t* iters, double* nr);
+
 /* The same solver for a GENERAL symmetric operator A -- the reference's LinearMap closure around hess_lag_vec! /
  * augmented_hess_lag_vec! (src/optimize.jl:228-230, applied at src/projcg.jl:57,74,116): `A(user, src, dest)` must produce
  * dest = A * src for device vectors of length(b) (stacked [x | gap | y] when U is a stacked basis), return 0, and leave

@@ -249,6 +249,13 @@ c_projcg_stencil(ctx, x, lam, a0, dg, off, K, dist, Av, U, b, c, tol, maxit, ngl
     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Cvoid}, Ref{CBasis}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Int64, Int64, Cint, Ref{CWork}, Ref{Int64}, Ref{Float64}),
     ctx, x, lam, a0, dg, off, K, dist, Av, U, b, c, tol, maxit, nglob, flags, work, iters, nr)
 c_stencil_mul(ctx, a0, dg, off, K, dist, v, out) = ccall((:lfpsqp_stencil_mul, lib), Cint, (Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Cvoid}, Ptr{Cvoid}), ctx, a0, dg, off, K, dist, v, out)
+c_sphess_create(ctx, n, nnz, rows, cols, vals, out) = ccall((:lfpsqp_sphess_create, lib), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ref{Ptr{Cvoid}}), ctx, n, nnz, rows, cols, vals, out)
+c_sphess_free(ctx, S) = ccall((:lfpsqp_sphess_free, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), ctx, S)
+c_sphess_info(S, n, nedges, kr, ke) = ccall((:lfpsqp_sphess_info, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}), S, n, nedges, kr, ke)
+c_sphess_mul(ctx, a0, dg, S, v, out) = ccall((:lfpsqp_sphess_mul, lib), Cint, (Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), ctx, a0, dg, S, v, out)
+c_projcg_sparse(ctx, x, lam, a0, dg, S, Av, U, b, c, tol, maxit, nglob, flags, work, iters, nr) = ccall((:lfpsqp_projcg_sparse, lib), Cint,
+    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{CBasis}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Int64, Int64, Cint, Ref{CWork}, Ref{Int64}, Ref{Float64}),
+    ctx, x, lam, a0, dg, S, Av, U, b, c, tol, maxit, nglob, flags, work, iters, nr)
 c_projcg_op(ctx, x, lam, A, user, Av, U, b, c, tol, maxit, nglob, flags, work, iters, nr) = ccall((:lfpsqp_projcg_op, lib), Cint,
     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{CBasis}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Int64, Int64, Cint, Ref{CWork}, Ref{Int64}, Ref{Float64}),
     ctx, x, lam, A, user, Av, U, b, c, tol, maxit, nglob, flags, work, iters, nr)
@@ -637,6 +644,39 @@ function LinearAlgebra.mul!(dest::DeviceVector, A::DiagonalsOperator, v::DeviceV
     return dest
 end
 
+# The symmetric off-diagonal part of a sparse Hessian (lfpsqp_sphess), from 1-based undirected edges (I[e], J[e]) with the entries V[e] = A_ij =
+# A_ji: any order, duplicates and mirrored duplicates add up, at most 32 entries per row; the values are constant over the handle's lifetime.
+mutable struct SparseHessian
+    ctx::HipContext
+    h::Ptr{Cvoid}
+    n::Int
+    nedges::Int
+    row_width::Int
+    edge_width::Int
+end
+function SparseHessian(ctx::HipContext, n::Integer, I::Vector{Int}, J::Vector{Int}, V::Vector{Float64})
+    length(I) == length(J) == length(V) || error("I, J and V are of different lengths")
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ctx, c_sphess_create(ctx.h, Int64(n), Int64(length(V)), Int64.(I .- 1), Int64.(J .- 1), V, r))
+    nn = Ref{Int64}(0); ne = Ref{Int64}(0); kr = Ref{Int64}(0); ke = Ref{Int64}(0)
+    check(ctx, c_sphess_info(r[], nn, ne, kr, ke))
+    S = SparseHessian(ctx, r[], Int(nn[]), Int(ne[]), Int(kr[]), Int(ke[]))
+    finalizer(x -> c_sphess_free(x.ctx.h, x.h), S)
+    return S
+end
+# (A v)_i = (a0 + dg_i) v_i + Σ_{j in row i of S} S_ij v_j: a diagonal Hessian plus couplings described by row indices (a mesh, a k-nearest-neighbour
+# graph, a grid in any numbering: what DiagonalsOperator cannot express).  projcg! keeps ONE pass over the basis per iteration with it
+# (lfpsqp_projcg_sparse); mul! is the LinearMap's action.
+struct SparseOperator
+    a0::Float64
+    dg::Union{Nothing,DeviceVector}
+    S::SparseHessian
+end
+function LinearAlgebra.mul!(dest::DeviceVector, A::SparseOperator, v::DeviceVector)
+    GC.@preserve A check(dest.ctx, c_sphess_mul(dest.ctx.h, A.a0, A.dg === nothing ? C_NULL : A.dg.h, A.S.h, v.h, dest.h))
+    return dest
+end
+
 # InequalityData(xl, xu) (src/inequality_helper.jl:39-89), device-resident q, r, s, t
 struct InequalityData
     q::DeviceVector
@@ -802,6 +842,21 @@ function projcg!(x::DeviceVector, λ::Union{Nothing,DeviceVector}, A::DiagonalsO
     rc = GC.@preserve U A solve(x.ctx.h, x.h, λ === nothing ? C_NULL : λ.h, A.a0, A.dg === nothing ? C_NULL : A.dg.h, A.off.h,
                                 Int64(length(A.dists)), pointer(A.dists), Av.h, Ref(cbasis(U)), b.h, c === nothing ? C_NULL : c.h, tol,
                                 Int64(maxit), Int64(n_global), flags, Ref(cwork(work)), iters, nr)
+    if rc == LFPSQP_ERR_UNSUPPORTED && !start_given
+        return projcg!(x, λ, (dest, src) -> mul!(dest, A, src), U, b, c; tol=tol, maxit=maxit, work=work, n_global=n_global)
+    end
+    check(x.ctx, rc)
+    return Int(iters[]), nr[]
+end
+# Sparse symmetric Hessian (couplings by row indices): the same rules (lfpsqp_projcg_sparse; A.S has N rows with a stacked basis)
+function projcg!(x::DeviceVector, λ::Union{Nothing,DeviceVector}, A::SparseOperator, U::AnyBasis, b::DeviceVector, c::Union{Nothing,DeviceVector};
+                 tol::Float64=1e-6, maxit::Int=length(b) + ncols(U), work::ProjCGWork=ProjCGWork(x, ncols(U)), n_global::Int=length(b),
+                 Av::DeviceVector=DeviceVector(x.ctx, length(b)), start_given::Bool=false)
+    iters = Ref{Int64}(0); nr = Ref{Float64}(0.0)
+    flags = (λ === nothing ? Cint(0) : LFPSQP_PROJCG_WANT_LAMBDA) | (start_given ? LFPSQP_PROJCG_START_GIVEN : Cint(0))
+    rc = GC.@preserve U A c_projcg_sparse(x.ctx.h, x.h, λ === nothing ? C_NULL : λ.h, A.a0, A.dg === nothing ? C_NULL : A.dg.h, A.S.h, Av.h,
+                                          Ref(cbasis(U)), b.h, c === nothing ? C_NULL : c.h, tol, Int64(maxit), Int64(n_global), flags,
+                                          Ref(cwork(work)), iters, nr)
     if rc == LFPSQP_ERR_UNSUPPORTED && !start_given
         return projcg!(x, λ, (dest, src) -> mul!(dest, A, src), U, b, c; tol=tol, maxit=maxit, work=work, n_global=n_global)
     end
@@ -1466,6 +1521,9 @@ hess_band(h) = nothing
 # A GRID-STENCIL one (a 2-D / 3-D field with a smoothness term): hess_diagonals(problem) returns (dists, off) -- up to four distances and an N x K
 # device matrix (column k couples variables i and i + dists[k]) -- or nothing; projcg! with a DiagonalsOperator under the same rules.
 hess_diagonals(h) = nothing
+# A SPARSE SYMMETRIC one (a graph smoothness term): hess_sparse(problem) returns a SparseHessian of N rows or nothing -- looked for after the three
+# above; projcg! with a SparseOperator under the same rules.
+hess_sparse(h) = nothing
 
 function optimize_core(ctx::HipContext, f, grad!, c!, jac!, hess_lag_vec!, x0::Vector{Float64}, xl, xu, m::Int, param::LFPSQPParams=LFPSQPParams();
                        n_global::Int=length(x0))
@@ -1504,7 +1562,7 @@ function optimize_core(ctx::HipContext, f, grad!, c!, jac!, hess_lag_vec!, x0::V
     # (the library says whether this context can run projcg! without Z for this Jct: one-pass kernels on, shape inside their limits, or a
     # sparse twin the nonzero path covers; otherwise Z is materialised and every path has its two-pass form)
     # (a tridiagonal Hessian sent through the callback path -- DeviceOptions.tridiagonal_one_pass off -- needs the materialised basis)
-    tri_callback = diagonal_hessian && (hess_offdiag(hess_lag_vec!) !== nothing || hess_band(hess_lag_vec!) !== nothing || hess_diagonals(hess_lag_vec!) !== nothing) && !ctx.options.tridiagonal_one_pass
+    tri_callback = diagonal_hessian && (hess_offdiag(hess_lag_vec!) !== nothing || hess_band(hess_lag_vec!) !== nothing || hess_diagonals(hess_lag_vec!) !== nothing || hess_sparse(hess_lag_vec!) !== nothing) && !ctx.options.tridiagonal_one_pass
     factored_basis = ctx.options.factored_basis && diagonal_hessian && !tri_callback && 4 <= m <= 1024 && factored_basis_supported(ctx, Jct, jsp === nothing ? C_NULL : jsp.h)
     # allocation by trial pays after several hundred projected-CG iterations; a Lagrangian Hessian that is a multiple of I (config 3) ends every
     # truncated-Newton solve after one: such a run takes its first allocations
@@ -1534,7 +1592,8 @@ function optimize_core(ctx::HipContext, f, grad!, c!, jac!, hess_lag_vec!, x0::V
     tri_off = diagonal_hessian ? hess_offdiag(hess_lag_vec!) : nothing
     band_off = (diagonal_hessian && tri_off === nothing) ? hess_band(hess_lag_vec!) : nothing
     diags_off = (diagonal_hessian && tri_off === nothing && band_off === nothing) ? hess_diagonals(hess_lag_vec!) : nothing
-    if tri_off !== nothing || band_off !== nothing || diags_off !== nothing           # (with bounds: the augmented stacked diagonal next to the same couplings)
+    sparse_off = (diagonal_hessian && tri_off === nothing && band_off === nothing && diags_off === nothing) ? hess_sparse(hess_lag_vec!) : nothing
+    if tri_off !== nothing || band_off !== nothing || diags_off !== nothing || sparse_off !== nothing           # (with bounds: the augmented stacked diagonal next to the same couplings)
         ctx.options.tridiagonal_one_pass || (fuse_tangent = false)     # (the callback path starts its solves itself)
         (haskey(VIEW_KEEP, Jct) || ctx.nranks > 1) && (fuse_tangent = false)  # (lfpsqp_projcg_tridiag refuses a matrix view / several ranks: callback path, its own start)
     end                                                       # (the tangent step still hands projcg! r0 and U'r0; never its folded initial projection)
@@ -1630,7 +1689,7 @@ function optimize_core(ctx::HipContext, f, grad!, c!, jac!, hess_lag_vec!, x0::V
                     hess_diag!(hess_lag_vec!, hdst, x, λ_kkt)
                 end
                 # the fold of projcg!'s initial projection: only where the Gram matrix resolves I - U'U (full rank, cond^2 <= 10)
-                init_fold = tri_off === nothing && band_off === nothing && diags_off === nothing && rank == m && Σ[1]^2 <= 10.0 * Σ[m]^2
+                init_fold = tri_off === nothing && band_off === nothing && diags_off === nothing && sparse_off === nothing && rank == m && Σ[1]^2 <= 10.0 * Σ[m]^2
                 GC.@preserve Ub cons_part begin
                     cref = cons_part === nothing ? nothing : Ref(ccons(cons_part))
                     iref = ineq ? Ref(cineq(idata)) : nothing
@@ -1712,6 +1771,15 @@ function optimize_core(ctx::HipContext, f, grad!, c!, jac!, hess_lag_vec!, x0::V
                                                   work=projcgwork, n_global=nglob, start_given=fused_now)
                     else
                         tn_iter, tn_res = projcg!(newton_d, nothing, (dest, src) -> mul!(dest, Adiags, src), Qview, d, nothing; tol=tol,
+                                                  maxit=param.tn_maxiter, work=projcgwork, n_global=nglob)
+                    end
+                elseif sparse_off !== nothing
+                    Asparse = SparseOperator(0.0, a_diag, sparse_off)
+                    if ctx.options.tridiagonal_one_pass
+                        tn_iter, tn_res = projcg!(newton_d, nothing, Asparse, Qview, d, nothing; tol=tol, maxit=param.tn_maxiter,
+                                                  work=projcgwork, n_global=nglob, start_given=fused_now)
+                    else
+                        tn_iter, tn_res = projcg!(newton_d, nothing, (dest, src) -> mul!(dest, Asparse, src), Qview, d, nothing; tol=tol,
                                                   maxit=param.tn_maxiter, work=projcgwork, n_global=nglob)
                     end
                 else
@@ -2046,7 +2114,7 @@ optimize(ctx::HipContext, f, grad!, c!, jac_c!, d!, jac_d!, hess_lag_vec!, x0::V
 
 export HipContext, HipError, DeviceOptions, DeviceVector, StackedVector, DeviceMatrix, SparseMatrix, spmv_t!, spmv_n!, to_dense!, DeviceBasis, DiagOperator, LowRankOperator, InequalityData, InequalityDecomp,
        InequalityDecompProject, ProjCGWork, DeviceConstraints, NR, ProjPenalty, ProjPenaltyWork, Euclidean, YRetract, ArmijoWork,
-       ExactLinesearchWork, LFPSQPParams, TerminationInfo, QuadLinearBallBox, SeparableLinearBallBox, ChainSeparableLinear, TridiagonalOperator, BandedOperator, DiagonalsOperator, SeparableElementwiseBox, ElementwiseConstraints,
+       ExactLinesearchWork, LFPSQPParams, TerminationInfo, QuadLinearBallBox, SeparableLinearBallBox, ChainSeparableLinear, TridiagonalOperator, BandedOperator, DiagonalsOperator, SparseHessian, SparseOperator, SeparableElementwiseBox, ElementwiseConstraints,
        sin_system_constraints, sphere_system_constraints, clone, rowscale!, set_placement!, basis_and_vectors_placed, vectors_placed, placement_info, upload!, download, upload2!, download2, projcg!, retract!,
        retract_nr_batch!, pcg!, ProjPrecondition, ksvd!, armijo!, exact_linesearch!, optimize, optimize_core, hess_diag!, jac!, comm_unique_id, comm_init!, comm_p2p_export, comm_init_p2p!,
        shard_range, sync

@@ -51,15 +51,22 @@ constexpr int kTLd = 17;
 // SHIFT = -1: the same operand with a RUN-TIME distance s >= 1 (the off-diagonals of a grid stencil, lfpsqp_projcg_diags; s arrives in `xoff`, which
 // a shifted launch does not need: it carries no extra columns): rows kh + s, kh + s + 1 by one aligned pair load for even s, two scalar loads for
 // odd s, zero from row n on.  For a far distance the partner rows are not in the lines the workgroup loads next: such a pass streams M twice.
+// SHIFT = -2: the GATHERED operand, R_i = M_i + sgn_i M_{p[i]} with the partner rows in an int32 index column p (the edge form of a sparse symmetric
+// Hessian, lfpsqp_projcg_sparse; p arrives in `ex0`, which a shifted launch does not use either, and holds a valid row for every row the steps
+// touch -- pad rows and rows without an edge carry the weight zero).  The partners of rows kh, kh + 1 come with one 8-byte load, issued a step
+// ahead of the matrix loads that depend on it; the two matrix entries per staged column are scalar loads (the partners of neighbouring rows
+// need not be neighbours).  How much of M such a pass streams a second time is the numbering's business: nothing for partners inside the chunk
+// of rows a workgroup walks anyway, everything for a random permutation.
 template <bool DIAG, bool WEIGHTED, int SHIFT = 0, int NX = 0>
 __global__ __launch_bounds__(kThreads, 2) void gram_kernel(const double* __restrict__ M, int64_t ld, int64_t n, int ncols, int npan,
                                                          int ngroups, const double* __restrict__ w2, double* __restrict__ part,
                                                          int64_t part_ld, const double* __restrict__ ex0, const double* __restrict__ ex1,
                                                          int64_t xoff, const double* __restrict__ sgn) {
     static_assert(SHIFT == 0 || WEIGHTED, "the shifted operand exists for weighted launches only");
-    static_assert(SHIFT >= -1 && SHIFT <= 4, "shift distances 1 .. 4, or -1: the distance at run time");
-    constexpr bool RT = SHIFT < 0;                      // run-time distance
-    constexpr bool PAIR = SHIFT > 1 || RT;              // the partner rows are a pair of their own
+    static_assert(SHIFT >= -2 && SHIFT <= 4, "shift distances 1 .. 4, -1: the distance at run time, -2: partner rows from an index column");
+    constexpr bool RT = SHIFT == -1;                    // run-time distance
+    constexpr bool GATH = SHIFT == -2;                  // gathered partner rows
+    constexpr bool PAIR = SHIFT > 1 || RT || GATH;      // the partner rows are a pair of their own
     // NX: how many of the extra right-hand columns (ex0, then ex1) this launch carries -- a compile-time fact: as run-time null tests of two
     // pointers the columns' multiply-adds were if-converted into 32 FMAs and ~37 compares / selects per two steps of EVERY launch, more vector
     // instructions than the rest of the loop has, between the matrix-core instructions of a wave (FINDINGS.md 12.8)
@@ -108,6 +115,10 @@ __global__ __launch_bounds__(kThreads, 2) void gram_kernel(const double* __restr
     const double* pb = M + ((int64_t)pj * kPanel + c) * ld + kh;
     const int na = ncols - pi * kPanel - c, nb = ncols - pj * kPanel - c;      // column c + 32 q of the panel exists iff 32 q < na / nb
     const int64_t cs = 32 * ld;
+    // GATH: the index column, the partners of the step loaded next (fetched while the step before it is loaded) and the end of this group's steps
+    const int* gidx = GATH ? reinterpret_cast<const int*>(ex0) : nullptr;
+    int2 gnext = make_int2(0, 0);
+    int64_t gnext_step = -1, gend = 0;
     // FULL: both panels have all their 128 columns (the usual case: then the loads are unconditional -- the per-column test costs an
     // exec-mask branch and a zero-fill per load in the loop)
     const bool full = ncols - pi * kPanel >= kPanel && ncols - pj * kPanel >= kPanel;
@@ -155,8 +166,16 @@ __global__ __launch_bounds__(kThreads, 2) void gram_kernel(const double* __restr
             // rows kh + k, kh + k + 1: zero from row n on (and there may lie outside the allocation); the pair load where both exist
             const int64_t sh = RT ? xoff : (int64_t)SHIFT;
             const bool b1 = r + kh + sh < n, b2 = r + kh + sh + 1 < n;
+            int2 gp = gnext;
+            if constexpr (GATH) {
+                if (gnext_step != step) gp = *reinterpret_cast<const int2*>(gidx + r + kh);
+                if (step + 1 < gend) { gnext = *reinterpret_cast<const int2*>(gidx + r + kKStep + kh); gnext_step = step + 1; }
+            }
             auto partner = [&](const double* p) -> double2 {
-                if constexpr (RT) {
+                if constexpr (GATH) {
+                    const double* col = p - (r + kh);             // row 0 of the staged column
+                    return make_double2(col[gp.x], col[gp.y]);
+                } else if constexpr (RT) {
                     if ((sh & 1) == 0 && b2) return ld2(p + sh);
                     return make_double2(b1 ? p[sh] : 0.0, b2 ? p[sh + 1] : 0.0);
                 } else if constexpr (SHIFT % 2 == 0) {
@@ -207,6 +226,7 @@ __global__ __launch_bounds__(kThreads, 2) void gram_kernel(const double* __restr
     const int64_t G = SHIFT ? 1 : ngroups;
     const int64_t send = SHIFT ? ((int64_t)(g + 1) * chunk < nsteps ? (int64_t)(g + 1) * chunk : nsteps) : nsteps;
     int64_t step = SHIFT ? (int64_t)g * chunk : g;
+    gend = send;
     double* out = part + (int64_t)g * part_ld + (int64_t)pidx * (kPanel * kPanel);
     // The MFMA operands of one k-group (4 of the 16 rows of a step): lane (kq = lane / 16, cc = lane % 16) holds row 4 kg + kq of
     // column cc of each 16-column tile it needs.  DIAG (symmetric block, upper tile triangle only -- the host mirrors it, gram_impl):
@@ -655,7 +675,8 @@ struct SqrtWTimesV {
 };
 
 static int gram_impl(lfpsqp_ctx* ctx, const lfpsqp_mat* M, int ncols_all, const double* w2, std::vector<double>& G, const GramRhs* rhs = nullptr,
-                     const double* shift_sgn = nullptr, int64_t shift = 1) {
+                     const double* shift_sgn = nullptr, int64_t shift = 1, const int32_t* gather = nullptr) {
+    // gather != NULL (with shift_sgn): R_i = M_i + shift_sgn_i M_{gather[i]} (gram_kernel SHIFT = -2; `shift` is not used)
     // shift_sgn != NULL: the Gram matrix of R, R_i = M_i + shift_sgn_i M_{i+shift} (gram_kernel SHIFT; a distance above 4 goes to the run-time
     // instantiation) -- plain matrix, weights given, no extra columns
     if (shift_sgn && (M->view || !w2 || rhs || shift < 1))
@@ -784,11 +805,13 @@ static int gram_impl(lfpsqp_ctx* ctx, const lfpsqp_mat* M, int ncols_all, const 
             auto launch_shifted = [&](auto Kc) {
                 constexpr int K = decltype(Kc)::value;
                 const int64_t xo = K < 0 ? shift : pp;        // (the run-time distance travels in the extra columns' offset, which no shifted launch uses)
-                hipLaunchKernelGGL((gram_kernel<true, true, K>), dim3(gd * npan), dim3(kThreads), 0, ctx->stream, M->p, M->ld, M->n, ncols, npan, gd, sw, ctx->part, pld, nullptr, nullptr, xo, shift_sgn);
+                const double* gx = K == -2 ? reinterpret_cast<const double*>(gather) : nullptr;     // (the index column travels in ex0)
+                hipLaunchKernelGGL((gram_kernel<true, true, K>), dim3(gd * npan), dim3(kThreads), 0, ctx->stream, M->p, M->ld, M->n, ncols, npan, gd, sw, ctx->part, pld, gx, nullptr, xo, shift_sgn);
                 if (noff > 0)
-                    hipLaunchKernelGGL((gram_kernel<false, true, K>), dim3(go * noff), dim3(kThreads), 0, ctx->stream, M->p, M->ld, M->n, ncols, npan, go, sw, ctx->part, pld, nullptr, nullptr, xo, shift_sgn);
+                    hipLaunchKernelGGL((gram_kernel<false, true, K>), dim3(go * noff), dim3(kThreads), 0, ctx->stream, M->p, M->ld, M->n, ncols, npan, go, sw, ctx->part, pld, gx, nullptr, xo, shift_sgn);
             };
-            switch (shift) {
+            if (gather) launch_shifted(std::integral_constant<int, -2>{});
+            else switch (shift) {
                 case 1: launch_shifted(std::integral_constant<int, 1>{}); break;
                 case 2: launch_shifted(std::integral_constant<int, 2>{}); break;
                 case 3: launch_shifted(std::integral_constant<int, 3>{}); break;
@@ -1327,6 +1350,15 @@ static int check_weights(lfpsqp_ctx* ctx, bool weighted, const std::vector<doubl
 // G (ncols x ncols, column-major) = R' diag(w) R for R_i = M_i + sgn_i M_{i+shift} (w >= 0 and sgn = +-1: device n-vectors; projcg.hip)
 int lfpsqp::gram_shifted(lfpsqp_ctx* ctx, const lfpsqp_mat* M, int ncols, const double* w, const double* sgn, std::vector<double>& G, int64_t shift) {
     LF_TRY(gram_impl(ctx, M, ncols, w, G, nullptr, sgn, shift));
+    return check_weights(ctx, true, G);
+}
+
+// G = R' diag(w) R for R_i = M_i + sgn_i M_{partner[i]} (partner: device int32 column, a valid row for every row up to the padded length).
+// Preconditions the caller owns (projcg_impl checks the first): the column describes M's rows -- every entry < M->n, at least round_up(M->n, 16)
+// of them --, and rows without a partner (pad rows among them) carry w = 0 and point at a row whose entries are finite (0 * M[row, col]).
+int lfpsqp::gram_gathered(lfpsqp_ctx* ctx, const lfpsqp_mat* M, int ncols, const double* w, const double* sgn, const int32_t* partner, std::vector<double>& G) {
+    LF_ARG(ctx, partner != nullptr);
+    LF_TRY(gram_impl(ctx, M, ncols, w, G, nullptr, sgn, 1, partner));
     return check_weights(ctx, true, G);
 }
 

@@ -571,6 +571,9 @@ int run_vec(lfpsqp_ctx* ctx, int64_t n, F f, unsigned ismax, double* red_out, PO
 // G = R' diag(w) R for R_i = M_i + sgn_i M_{i+shift} (shift >= 1; above 4 at run time) on the matrix cores (factorize.hip, gram_kernel SHIFT); plain M, w >= 0,
 // sgn = +-1 (device)
 int gram_shifted(lfpsqp_ctx* ctx, const lfpsqp_mat* M, int ncols, const double* w, const double* sgn, std::vector<double>& G, int64_t shift = 1);
+// ... and for R_i = M_i + sgn_i M_{partner[i]}: the partner rows gathered through a device int32 column (gram_kernel SHIFT = -2), which holds a
+// valid row index for every row up to round_up(n, 16) (rows without a partner: any row, with w = 0)
+int gram_gathered(lfpsqp_ctx* ctx, const lfpsqp_mat* M, int ncols, const double* w, const double* sgn, const int32_t* partner, std::vector<double>& G);
 
 // one-sided Jacobi on the columns of a small host matrix, run on the device (jacobi.hip); false = shape not covered
 bool device_jacobi(lfpsqp_ctx* ctx, int rows_dot, int rows_all, int cols, std::vector<double>& X, int* sweeps_out = nullptr);

@@ -44,6 +44,7 @@
 
 #include "internal.h"
 #include "sparse.h"
+#include "sphess.h"
 
 namespace lfpsqp {
 
@@ -384,9 +385,9 @@ struct DiagsD {
         return o;
     }
 };
-template <int C>
+template <class D>       // D: DiagsD<C>, or SpHessD (sphess.h) -- the same interface, the neighbours from a row's index slots
 struct DiagsMulF {   // out = A v
-    DiagsD<C> A;
+    D A;
     const double* v;
     double* out;
     const int64_t* istat;     // nullptr: always; else only while the solve is running
@@ -409,9 +410,9 @@ struct DiagsMulF {   // out = A v
 // (DiagsMulF, while the solve runs) and this kernel gathers  q_i = sum_k (off_k[i-s_k] rr_{i-s_k} + off_k[i] rr_{i+s_k})  from
 // rr = g + alpha ad at the shifted rows (the same fma as the pass forms for its own row).  ad == nullptr: rr = g as stored -- the initial
 // residual (INIT), or the projected residual ux that DiagsPrepSF left for a stacked basis.
-template <int C>
+template <class D>
 struct DiagsGatherF {
-    DiagsD<C> A;              // n = nc = the rows with couplings
+    D A;                      // n = nc = the rows with couplings
     const double* g;
     const double* ad;
     double* q;
@@ -438,9 +439,9 @@ struct DiagsGatherF {
 // Stacked basis (PcgFuseTri<true, .>), the row-local half of TriPrepSF:  ad = (T d)_x  and the x half of the residual projected off the diagonal
 // block,  ux_r = rx_r - Dx_r (Dx_r rx_r + Dy_r ry_r)  with  rr = g + alpha A d  (the pass's own expressions), stored once so that DiagsGatherF can
 // gather it at the far rows.  INIT: rr is the stored initial residual, only ux is written.
-template <int C, bool INIT>
+template <class D, bool INIT>
 struct DiagsPrepSF {
-    DiagsD<C> A;              // n = nc = N; dg stacked (the y half at dg + hs)
+    D A;                      // n = nc = N; dg stacked (the y half at dg + hs)
     int64_t hs;
     const double *Dx, *Dy;
     const double* g;
@@ -1460,27 +1461,18 @@ static int tri_weights_alloc(lfpsqp_ctx* ctx, int64_t n, int K, bool stacked, Tr
 }
 // Mh = sum_k R_k' diag(|off_k|) R_k + Z' diag(cpos) Z - Z' diag(cneg) Z from the prepared weights (dist[k]: the row distance of column k), then
 // W'(.)W for a basis in factored form
-static int reduced_from_weights(lfpsqp_ctx* ctx, const lfpsqp_mat* Z, int mc, int64_t n, int K, const int64_t* dist, const TriWeights& w,
-                                const double* W, int m, std::vector<double>& Mh) {
-    const int64_t npad = w.npad;
-    double hneg = 0.0;
-    LF_HIP(ctx, hipMemcpyAsync(&hneg, w.anyneg, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const lfpsqp_mat Zp = Z->plain();
-    std::vector<double> G, G2((size_t)mc * mc);
-    LF_TRY(gram_shifted(ctx, &Zp, mc, w.wabs, w.sgn, G, dist[0]));
-    for (int k = 2; k <= K; ++k) {
-        LF_TRY(gram_shifted(ctx, &Zp, mc, w.wabs + (k - 1) * npad, w.sgn + (k - 1) * npad, G2, dist[k - 1]));
-        for (size_t e = 0; e < G.size(); ++e) G[e] += G2[e];
-    }
-    G2.resize((size_t)mc * mc);
+// G (mc x mc: the sum of the coupling passes) + Z' diag(cpos) Z - Z' diag(cneg) Z (the second pass only with hneg != 0), then W'(.)W for a basis in
+// factored form -> Mh
+static int reduced_finish(lfpsqp_ctx* ctx, const lfpsqp_mat& Zp, int mc, int64_t n, int64_t npad, double* cpos, double* cneg, double hneg,
+                          const double* W, int m, std::vector<double>& G, std::vector<double>& Mh) {
+    std::vector<double> G2((size_t)mc * mc);
     lfpsqp_vec wv;
     wv.n = n; wv.cap = npad;
-    wv.p = w.cpos;
+    wv.p = cpos;
     LF_TRY(lfpsqp_gram(ctx, &Zp, mc, &wv, G2.data()));
     for (size_t k = 0; k < G.size(); ++k) G[k] += G2[k];
     if (hneg != 0.0) {
-        wv.p = w.cneg;
+        wv.p = cneg;
         LF_TRY(lfpsqp_gram(ctx, &Zp, mc, &wv, G2.data()));
         for (size_t k = 0; k < G.size(); ++k) G[k] -= G2[k];
     }
@@ -1502,6 +1494,21 @@ static int reduced_from_weights(lfpsqp_ctx* ctx, const lfpsqp_mat* Z, int mc, in
         }
     return 0;
 }
+static int reduced_from_weights(lfpsqp_ctx* ctx, const lfpsqp_mat* Z, int mc, int64_t n, int K, const int64_t* dist, const TriWeights& w,
+                                const double* W, int m, std::vector<double>& Mh) {
+    const int64_t npad = w.npad;
+    double hneg = 0.0;
+    LF_HIP(ctx, hipMemcpyAsync(&hneg, w.anyneg, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const lfpsqp_mat Zp = Z->plain();
+    std::vector<double> G, G2((size_t)mc * mc);
+    LF_TRY(gram_shifted(ctx, &Zp, mc, w.wabs, w.sgn, G, dist[0]));
+    for (int k = 2; k <= K; ++k) {
+        LF_TRY(gram_shifted(ctx, &Zp, mc, w.wabs + (k - 1) * npad, w.sgn + (k - 1) * npad, G2, dist[k - 1]));
+        for (size_t e = 0; e < G.size(); ++e) G[e] += G2[e];
+    }
+    return reduced_finish(ctx, Zp, mc, n, npad, w.cpos, w.cneg, hneg, W, m, G, Mh);
+}
 // Mh (m x m, column-major, host) = U'A U for U = Z[:, :mc] (W == nullptr, m == mc) or U = Z[:, :mc] W (W: mc x m, host); sk: a stacked basis,
 // U = [sx; sy] .* (that), and A over the x half (A0.n = A0.nc = N, the rows of Z; dg stacked)
 template <int C>
@@ -1522,13 +1529,87 @@ static int reduced_operator(lfpsqp_ctx* ctx, const lfpsqp_mat* Z, int mc, const 
     return reduced_from_weights(ctx, Z, mc, n, A0.K, A0.s, w, W, m, Mh);
 }
 
+// ---- the same for a sparse symmetric Hessian (lfpsqp_sphess) --------------------------------------------------------------------------------
+// The identity above does not care where the partner of a coupling sits: with every undirected edge stored once, at its owner (the edge form of
+// lfpsqp_sphess: slot k of row i holds the partner p_k[i] and the coupling w_k[i]),
+//     Z'A Z = sum_{k < Ke} R_k' diag(|w_k|) R_k + Z' diag(c) Z,    R_{k,i} = Z_i + sign(w_k[i]) Z_{p_k[i]},    c_i = a0 + dg_i - sum_j |A_ij|,
+// Ke + 1 or Ke + 2 weighted Gram passes whose operand GATHERS the partner rows (gram_kernel SHIFT = -2), no n x m scratch matrix.  The weights of a
+// pass are two n-vectors formed right before it (|w_k| and sign(w_k): 4 npad doubles of scratch in all, whatever Ke); c comes from the row form
+// (all of a row's neighbours, slot order).  Stacked basis: the couplings of At = S_x A S_x + S_y diag(ay) S_y, At_ij = A_ij (sx_i sx_j) -- the
+// product of the two scalings first, so that both endpoints of an edge see the same bits.
+// Summed in the order k = 0 .. Ke - 1, + cpos, - cneg.
+__global__ __launch_bounds__(256) void sphess_diag_weights_kernel(SpHessD A, int64_t hs, const double* __restrict__ sx, const double* __restrict__ sy,
+                                                                  double* __restrict__ cpos, double* __restrict__ cneg, double* __restrict__ anyneg) {
+    bool neg = false;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < A.npad; i += (int64_t)gridDim.x * 256) {
+        double cp = 0.0, cn = 0.0;
+        if (i < A.n) {
+            const double ax = A.a0 + (A.dg ? A.dg[i] : 0.0);
+            double c = ax;
+            if (sx) {
+                const double ay = A.a0 + (A.dg ? A.dg[hs + i] : 0.0);
+                c = fma(sx[i] * sx[i], ax, sy[i] * sy[i] * ay);
+            }
+            for (int k = 0; k < A.K; ++k) {
+                const int64_t j = A.idx[(int64_t)k * A.npad + i];
+                double w = A.val[(int64_t)k * A.npad + i];
+                if (sx) w *= sx[i] * sx[j];
+                c -= fabs(w);
+            }
+            if (c >= 0.0) cp = c;
+            else { cn = -c; neg = true; }
+            if (c != c) cp = c;                               // (NaN data: let the Gram pass report it)
+        }
+        cpos[i] = cp; cneg[i] = cn;
+    }
+    if (neg) *anyneg = 1.0;
+}
+// the weights of the Gram pass of edge slot k: |w_k| and sign(w_k) (pad rows and empty slots: 0 and +1)
+__global__ __launch_bounds__(256) void sphess_edge_weights_kernel(const int32_t* __restrict__ eidx, const double* __restrict__ eval, int64_t n, int64_t npad,
+                                                                  const double* __restrict__ sx, double* __restrict__ wabs, double* __restrict__ sgn) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < npad; i += (int64_t)gridDim.x * 256) {
+        double w = i < n ? eval[i] : 0.0;
+        if (sx && i < n) w *= sx[i] * sx[eidx[i]];
+        wabs[i] = fabs(w);
+        sgn[i] = (w < 0.0) ? -1.0 : 1.0;
+    }
+}
+static int reduced_operator_sparse(lfpsqp_ctx* ctx, const lfpsqp_mat* Z, int mc, double a0, const double* dg, const lfpsqp_sphess& S, const double* W,
+                                   int m, std::vector<double>& Mh, const StackD* sk = nullptr) {
+    const int64_t n = S.n, npad = S.npad;
+    LF_TRY(ensure_tri(ctx, 4 * (size_t)npad + 8));
+    double *wabs = ctx->d_tri, *sgn = wabs + npad, *cpos = sgn + npad, *cneg = cpos + npad, *anyneg = cneg + npad;
+    const unsigned nblk = (unsigned)std::min<int64_t>((npad + 255) / 256, 4096);
+    const double *sx = sk ? sk->sx : nullptr, *sy = sk ? sk->sy : nullptr;
+    LF_HIP(ctx, hipMemsetAsync(anyneg, 0, sizeof(double), ctx->stream));
+    hipLaunchKernelGGL(sphess_diag_weights_kernel, dim3(nblk), dim3(256), 0, ctx->stream, SpHessD{a0, dg, S.ridx, S.rval, npad, n, n, S.Kr},
+                       sk ? sk->hs : (int64_t)0, sx, sy, cpos, cneg, anyneg);
+    LF_LAUNCH_CHECK(ctx);
+    double hneg = 0.0;
+    LF_HIP(ctx, hipMemcpyAsync(&hneg, anyneg, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const lfpsqp_mat Zp = Z->plain();
+    std::vector<double> G((size_t)mc * mc, 0.0), G2;
+    for (int k = 0; k < S.Ke; ++k) {
+        const int32_t* pk = S.eidx + (int64_t)k * npad;
+        hipLaunchKernelGGL(sphess_edge_weights_kernel, dim3(nblk), dim3(256), 0, ctx->stream, pk, S.eval + (int64_t)k * npad, n, npad, sx, wabs, sgn);
+        LF_LAUNCH_CHECK(ctx);
+        LF_TRY(gram_gathered(ctx, &Zp, mc, wabs, sgn, pk, k == 0 ? G : G2));
+        if (k > 0)
+            for (size_t e = 0; e < G.size(); ++e) G[e] += G2[e];
+    }
+    return reduced_finish(ctx, Zp, mc, n, npad, cpos, cneg, hneg, W, m, G, Mh);
+}
+
 // A coupled operator as its entry point describes it: K coupling columns of `rows` entries, ld apart, next to the diagonal (a0, dg).
 //   BAND   column k couples rows i and i + k + 1, K = the bandwidth (1 .. 4) is a compile-time parameter of the kernels (BandD<K>, register
 //          windows): lfpsqp_projcg_tridiag (K = 1, off a vector), lfpsqp_projcg_band (off a plain matrix) and their _mul;
 //   DIAGS  column k couples rows i and i + dist[k], run-time distances (DiagsD, gathers): lfpsqp_projcg_diags, lfpsqp_diags_mul (K <= 4) and
-//          lfpsqp_projcg_stencil, lfpsqp_stencil_mul (K <= 13; more than four distances run the kernels of the wide descriptor).
+//          lfpsqp_projcg_stencil, lfpsqp_stencil_mul (K <= 13; more than four distances run the kernels of the wide descriptor);
+//   SPARSE the couplings of row i are the entries of its index slots (lfpsqp_sphess, K = its row width; SpHessD, the functors of DIAGS):
+//          lfpsqp_projcg_sparse, lfpsqp_sphess_mul.  No coupling columns: off == nullptr, rows = the rows of `sp`.
 struct CoupledOp {
-    enum Kind { BAND, DIAGS } kind;
+    enum Kind { BAND, DIAGS, SPARSE } kind;
     const char* who;          // the entry point, for messages
     double a0;
     const lfpsqp_vec* dg;
@@ -1536,6 +1617,7 @@ struct CoupledOp {
     int64_t ld, rows;
     int K;
     int64_t dist[kDiagsWide]; // BAND: {1, 2, 3, 4}
+    const lfpsqp_sphess* sp = nullptr;   // SPARSE
     const double* dgp() const { return dg ? dg->p : nullptr; }
     // over vectors of n rows, couplings on the first nc
     template <int C>
@@ -1545,8 +1627,12 @@ struct CoupledOp {
         return A;
     }
     bool wide() const { return K > kDiagsNarrow; }
+    SpHessD sparse(int64_t n, int64_t nc) const { return SpHessD{a0, dgp(), sp->ridx, sp->rval, sp->npad, n, nc, sp->Kr}; }
     template <int B>
     BandD<B> band(int64_t n, int64_t nc) const { return BandD<B>{a0, dgp(), off, ld, n, nc}; }
+    static CoupledOp sparse_of(const char* who, double a0, const lfpsqp_vec* dg, const lfpsqp_sphess* S) {
+        return CoupledOp{SPARSE, who, a0, dg, nullptr, 0, S->n, S->Kr, {}, S};
+    }
     static CoupledOp banded(const char* who, double a0, const lfpsqp_vec* dg, const double* off, int64_t ld, int64_t rows, int bw) {
         return CoupledOp{BAND, who, a0, dg, off, ld, rows, bw, {1, 2, 3, 4}};
     }
@@ -1555,6 +1641,13 @@ struct CoupledOp {
 template <typename F>
 static int with_diags(const CoupledOp& A, F&& fn) {
     return A.wide() ? fn(std::integral_constant<int, kDiagsWide>{}) : fn(std::integral_constant<int, kDiagsNarrow>{});
+}
+// fn(descriptor) for an operator whose neighbours are gathered (DIAGS: DiagsD of the capacity that holds the distances; SPARSE: SpHessD), over
+// vectors of n rows, couplings on the first nc
+template <typename F>
+static int with_gathers(const CoupledOp& A, int64_t n, int64_t nc, F&& fn) {
+    if (A.kind == CoupledOp::SPARSE) return fn(A.sparse(n, nc));
+    return with_diags(A, [&](auto Cc) -> int { return fn(A.template diags<decltype(Cc)::value>(n, nc)); });
 }
 // fn(std::integral_constant<int, B>) for B = bw (1 .. 4)
 template <typename F>
@@ -1569,10 +1662,10 @@ static int with_band(int bw, F&& fn) {
 
 // out = A v over vectors of n rows, couplings on the first nc
 static int coupled_mul(lfpsqp_ctx* ctx, const CoupledOp& A, int64_t n, int64_t nc, const double* v, double* out) {
-    if (A.kind == CoupledOp::DIAGS)
-        return with_diags(A, [&](auto Cc) -> int {
-            constexpr int C = decltype(Cc)::value;
-            return run_vec<DiagsMulF<C>, 0, NoPost>(ctx, n, DiagsMulF<C>{A.template diags<C>(n, nc), v, out, nullptr}, 0u, nullptr, NoPost());
+    if (A.kind != CoupledOp::BAND)
+        return with_gathers(A, n, nc, [&](auto Ad) -> int {
+            using D = decltype(Ad);
+            return run_vec<DiagsMulF<D>, 0, NoPost>(ctx, n, DiagsMulF<D>{Ad, v, out, nullptr}, 0u, nullptr, NoPost());
         });
     return with_band(A.K, [&](auto Bc) -> int {
         constexpr int B = decltype(Bc)::value;
@@ -1710,12 +1803,15 @@ static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const
     std::vector<double> triMh;
     if (cop) {
         // (stacked: dg over both halves, off the x half's couplings -- N rows; the y half is diagonal)
-        LF_ARG(ctx, cop->off && cop->rows == N && cop->K >= 1 && cop->K <= (cop->kind == CoupledOp::DIAGS ? kDiagsWide : kDiagsNarrow) && (!cop->dg || cop->dg->n == nv));
+        if (cop->kind == CoupledOp::SPARSE) LF_ARG(ctx, cop->sp && cop->rows == N && (!cop->dg || cop->dg->n == nv));
+        else LF_ARG(ctx, cop->off && cop->rows == N && cop->K >= 1 && cop->K <= (cop->kind == CoupledOp::DIAGS ? kDiagsWide : kDiagsNarrow) && (!cop->dg || cop->dg->n == nv));
         if (!fused || !plain_mat(Z) || ctx->comm_active())
             return set_err(ctx, LFPSQP_ERR_UNSUPPORTED, "%s: needs the one-pass iteration over a dense basis (4 .. 1024 columns, no matrix "
                                                         "view) on a single rank (the couplings would cross the shard boundaries); use lfpsqp_projcg_op",
                            cop->who);
-        LF_TRY(with_diags(*cop, [&](auto Cc) -> int {
+        if (cop->kind == CoupledOp::SPARSE)
+            LF_TRY(reduced_operator_sparse(ctx, Z, mc, cop->a0, cop->dgp(), *cop->sp, DF ? U->W : nullptr, m, triMh, stacked ? &sk : nullptr));
+        else LF_TRY(with_diags(*cop, [&](auto Cc) -> int {
             return reduced_operator(ctx, Z, mc, cop->template diags<decltype(Cc)::value>(N, N), DF ? U->W : nullptr, m, triMh, stacked ? &sk : nullptr);
         }));
     }
@@ -1837,18 +1933,17 @@ static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const
                 if constexpr (ST) return run_vec<TriPrepSF<B, INIT>, 0, NoPost>(ctx, N, TriPrepSF<B, INIT>{Ab, hs, sk.Dx, sk.Dy, src, dsrc, ad, q, scal, istat}, 0u, nullptr, NoPost());
                 else return run_vec<TriPrepF<B, INIT>, 0, NoPost>(ctx, N, TriPrepF<B, INIT>{Ab, src, dsrc, ad, q, scal, istat}, 0u, nullptr, NoPost());
             });
-        // run-time distances: A d stored first, then the gather of the neighbours' rr (stacked: of ux, kept in the set-up's scratch, which is
-        // free once M is on the device)
-        return with_diags(*cop, [&](auto Cc) -> int {
-            constexpr int C = decltype(Cc)::value;
-            const DiagsD<C> Ab = cop->template diags<C>(N, N);
+        // run-time distances or index slots: A d stored first, then the gather of the neighbours' rr (stacked: of ux, kept in the set-up's scratch,
+        // which is free once M is on the device)
+        return with_gathers(*cop, N, N, [&](auto Ab) -> int {
+            using D = decltype(Ab);
             if constexpr (ST) {
                 double* ux = ctx->d_tri;
-                LF_TRY((run_vec<DiagsPrepSF<C, INIT>, 0, NoPost>(ctx, N, DiagsPrepSF<C, INIT>{Ab, hs, sk.Dx, sk.Dy, src, dsrc, ad, ux, scal, istat}, 0u, nullptr, NoPost())));
-                return run_vec<DiagsGatherF<C>, 0, NoPost>(ctx, N, DiagsGatherF<C>{Ab, ux, nullptr, q, scal, istat}, 0u, nullptr, NoPost());
+                LF_TRY((run_vec<DiagsPrepSF<D, INIT>, 0, NoPost>(ctx, N, DiagsPrepSF<D, INIT>{Ab, hs, sk.Dx, sk.Dy, src, dsrc, ad, ux, scal, istat}, 0u, nullptr, NoPost())));
+                return run_vec<DiagsGatherF<D>, 0, NoPost>(ctx, N, DiagsGatherF<D>{Ab, ux, nullptr, q, scal, istat}, 0u, nullptr, NoPost());
             } else {
-                if constexpr (!INIT) LF_TRY((run_vec<DiagsMulF<C>, 0, NoPost>(ctx, N, DiagsMulF<C>{Ab, dsrc, ad, istat}, 0u, nullptr, NoPost())));
-                return run_vec<DiagsGatherF<C>, 0, NoPost>(ctx, N, DiagsGatherF<C>{Ab, src, ad, q, scal, istat}, 0u, nullptr, NoPost());
+                if constexpr (!INIT) LF_TRY((run_vec<DiagsMulF<D>, 0, NoPost>(ctx, N, DiagsMulF<D>{Ab, dsrc, ad, istat}, 0u, nullptr, NoPost())));
+                return run_vec<DiagsGatherF<D>, 0, NoPost>(ctx, N, DiagsGatherF<D>{Ab, src, ad, q, scal, istat}, 0u, nullptr, NoPost());
             }
         });
     };
@@ -2170,6 +2265,20 @@ extern "C" int lfpsqp_stencil_mul(lfpsqp_ctx* ctx, double a0, const lfpsqp_vec* 
     CoupledOp A;
     LF_TRY(diags_op(ctx, "lfpsqp_stencil_mul", a0, dg, off, K, dist, kDiagsWide, A));
     return coupled_mul_entry(ctx, A, v, out);
+}
+
+extern "C" int lfpsqp_projcg_sparse(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, double a0, const lfpsqp_vec* dg, const lfpsqp_sphess* S,
+                                    lfpsqp_vec* Av, const lfpsqp_basis* U, const lfpsqp_vec* b, const lfpsqp_vec* c, double tol, int64_t maxit,
+                                    int64_t n_global, int flags, const lfpsqp_projcg_work* work, int64_t* iters, double* nr) {
+    LF_RANGE("lfpsqp_projcg_sparse");
+    LF_ARG(ctx, ctx && Av && S);
+    return projcg_coupled(ctx, x, lambda, CoupledOp::sparse_of("lfpsqp_projcg_sparse", a0, dg, S), Av, U, b, c, tol, maxit, n_global, flags, work, iters,
+                          nr);
+}
+
+extern "C" int lfpsqp_sphess_mul(lfpsqp_ctx* ctx, double a0, const lfpsqp_vec* dg, const lfpsqp_sphess* S, const lfpsqp_vec* v, lfpsqp_vec* out) {
+    LF_ARG(ctx, ctx && S);
+    return coupled_mul_entry(ctx, CoupledOp::sparse_of("lfpsqp_sphess_mul", a0, dg, S), v, out);
 }
 
 extern "C" int lfpsqp_projcg_op(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, lfpsqp_opfun A, void* user, lfpsqp_vec* Av,

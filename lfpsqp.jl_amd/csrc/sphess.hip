@@ -1,0 +1,118 @@
+// lfpsqp_sphess: a symmetric sparse Hessian's off-diagonal part, built once on the host from triplets into the two ELL forms of sphess.h.
+// The kernels that read them live with the solver (projcg.hip: products, gathers, set-up weights) and with the Gram kernel (factorize.hip: the
+// gathered operand).
+#include <math.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "sphess.h"
+
+using namespace lfpsqp;
+
+namespace {
+struct Edge {
+    int32_t i, j;       // i < j
+    double v;
+};
+}  // namespace
+
+extern "C" {
+
+int lfpsqp_sphess_create(lfpsqp_ctx* ctx, int64_t n, int64_t nnz, const int64_t* rows, const int64_t* cols, const double* vals, lfpsqp_sphess** out) {
+    LF_ARG(ctx, ctx && out && n >= 0 && nnz >= 0 && (nnz == 0 || (rows && cols && vals)));
+    *out = nullptr;
+    if (n >= ((int64_t)1 << 31)) return set_err(ctx, LFPSQP_ERR_UNSUPPORTED, "sphess: %lld rows (indices are stored as int32)", (long long)n);
+    std::vector<Edge> ed((size_t)nnz);
+    bool sorted = true;
+    for (int64_t e = 0; e < nnz; ++e) {
+        const int64_t i = rows[e], j = cols[e];
+        if (i < 0 || i >= n || j < 0 || j >= n) return set_err(ctx, LFPSQP_ERR_ARG, "sphess: entry %lld out of range", (long long)e);
+        if (i == j) return set_err(ctx, LFPSQP_ERR_ARG, "sphess: entry %lld lies on the diagonal (the diagonal is dg)", (long long)e);
+        if (!std::isfinite(vals[e])) return set_err(ctx, LFPSQP_ERR_ARG, "sphess: entry %lld is not finite", (long long)e);
+        ed[(size_t)e] = Edge{(int32_t)std::min(i, j), (int32_t)std::max(i, j), vals[e]};
+        if (e > 0 && sorted) {
+            const Edge& p = ed[(size_t)e - 1];
+            sorted = p.i < ed[(size_t)e].i || (p.i == ed[(size_t)e].i && p.j <= ed[(size_t)e].j);
+        }
+    }
+    // lexicographic (i, j), i < j; duplicates (a mirrored (j, i) included) add up in the order they were given; a sum of zero keeps its slot
+    if (!sorted) std::stable_sort(ed.begin(), ed.end(), [](const Edge& a, const Edge& b) { return a.i != b.i ? a.i < b.i : a.j < b.j; });
+    size_t ne = 0;
+    for (size_t e = 0; e < ed.size(); ++e) {
+        if (ne > 0 && ed[ne - 1].i == ed[e].i && ed[ne - 1].j == ed[e].j) ed[ne - 1].v += ed[e].v;
+        else ed[ne++] = ed[e];
+    }
+    ed.resize(ne);
+    std::vector<int32_t> deg((size_t)std::max<int64_t>(n, 1), 0), own((size_t)std::max<int64_t>(n, 1), 0);
+    std::vector<uint8_t> at_j(ne, 0);
+    int Kr = 0, Ke = 0;
+    for (size_t e = 0; e < ne; ++e) {
+        const int32_t i = ed[e].i, j = ed[e].j;
+        Kr = std::max(Kr, std::max(++deg[(size_t)i], ++deg[(size_t)j]));
+        // the owner: j if it owns strictly fewer edges so far, otherwise i
+        at_j[e] = own[(size_t)j] < own[(size_t)i];
+        Ke = std::max(Ke, ++own[(size_t)(at_j[e] ? j : i)]);
+    }
+    if (Kr > LFPSQP_SPHESS_MAX_ROW)
+        return set_err(ctx, LFPSQP_ERR_UNSUPPORTED, "sphess: a row with %d off-diagonal entries (> %d)", Kr, LFPSQP_SPHESS_MAX_ROW);
+    lfpsqp_sphess* S = new lfpsqp_sphess();
+    S->n = n; S->nedges = (int64_t)ne; S->Kr = Kr; S->Ke = Ke;
+    S->npad = round_up((n > 0 ? n : 1) + 1, kPadRows);
+    const size_t npad = (size_t)S->npad, rsz = (size_t)std::max(Kr, 1) * npad, esz = (size_t)std::max(Ke, 1) * npad;
+    std::vector<int32_t> ri(rsz, 0), ei(esz, 0);
+    std::vector<double> rv(rsz, 0.0), ev(esz, 0.0);
+    for (int64_t r = 0; r < n; ++r) {
+        for (int k = 0; k < std::max(Kr, 1); ++k) ri[(size_t)k * npad + (size_t)r] = (int32_t)r;
+        for (int k = 0; k < std::max(Ke, 1); ++k) ei[(size_t)k * npad + (size_t)r] = (int32_t)r;
+    }
+    // (in lexicographic order every edge (i, r), i < r, comes before every edge (r, j), r < j: a row's slots fill in increasing neighbour order)
+    std::fill(deg.begin(), deg.end(), 0);
+    std::fill(own.begin(), own.end(), 0);
+    for (size_t e = 0; e < ne; ++e) {
+        const int32_t i = ed[e].i, j = ed[e].j;
+        const size_t si = (size_t)deg[(size_t)i]++ * npad + (size_t)i, sj = (size_t)deg[(size_t)j]++ * npad + (size_t)j;
+        ri[si] = j; rv[si] = ed[e].v;
+        ri[sj] = i; rv[sj] = ed[e].v;
+        const int32_t o = at_j[e] ? j : i, p = at_j[e] ? i : j;
+        const size_t so = (size_t)own[(size_t)o]++ * npad + (size_t)o;
+        ei[so] = p; ev[so] = ed[e].v;
+    }
+    bool ok = true;
+    auto dev_copy = [&](void** dst, const void* src, size_t bytes) {
+        if (!ok) return;
+        ok = hipMalloc(dst, bytes) == hipSuccess;
+        if (ok) ok = hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
+    };
+    dev_copy((void**)&S->ridx, ri.data(), rsz * sizeof(int32_t));
+    dev_copy((void**)&S->rval, rv.data(), rsz * sizeof(double));
+    dev_copy((void**)&S->eidx, ei.data(), esz * sizeof(int32_t));
+    dev_copy((void**)&S->eval, ev.data(), esz * sizeof(double));
+    if (ok) ok = hipStreamSynchronize(ctx->stream) == hipSuccess;
+    if (!ok) {
+        lfpsqp_sphess_free(ctx, S);
+        return set_err(ctx, LFPSQP_ERR_HIP, "sphess: device allocation / upload failed");
+    }
+    *out = S;
+    return 0;
+}
+
+int lfpsqp_sphess_free(lfpsqp_ctx* ctx, lfpsqp_sphess* S) {
+    if (!S) return 0;
+    if (ctx) (void)hipStreamSynchronize(ctx->stream);
+    for (void* p : {(void*)S->ridx, (void*)S->rval, (void*)S->eidx, (void*)S->eval})
+        if (p) (void)hipFree(p);
+    delete S;
+    return 0;
+}
+
+int lfpsqp_sphess_info(const lfpsqp_sphess* S, int64_t* n, int64_t* nedges, int64_t* row_width, int64_t* edge_width) {
+    if (!S) return LFPSQP_ERR_ARG;
+    if (n) *n = S->n;
+    if (nedges) *nedges = S->nedges;
+    if (row_width) *row_width = S->Kr;
+    if (edge_width) *edge_width = S->Ke;
+    return 0;
+}
+
+}  // extern "C"

@@ -116,11 +116,11 @@ def _amax_host(v):
 
 def _coupled_operator(ctx, hess_lag_vec_):
     """The Newton map of a Lagrangian Hessian that is diagonal plus couplings, or None.  Next to ``diag_`` the class exposes ONE of (looked for
-    in this order) ``offdiag`` (n-vector: :class:`TridiagonalOperator`), ``offdiags`` (N x bw matrix: :class:`BandedOperator`) or ``diagonals`` =
-    (dists, off) (:class:`DiagonalsOperator`); projcg_ keeps one pass per iteration with each unless DeviceOptions.tridiagonal_one_pass is off
+    in this order) ``offdiag`` (n-vector: :class:`TridiagonalOperator`), ``offdiags`` (N x bw matrix: :class:`BandedOperator`), ``diagonals`` =
+    (dists, off) (:class:`DiagonalsOperator`) or ``sparse_hessian`` (a :class:`SparseHessian` of N rows: :class:`SparseOperator`); projcg_ keeps one pass per iteration with each unless DeviceOptions.tridiagonal_one_pass is off
     (``fused``).  With bounds the Newton map is blockdiag(H + 2 lamy.*q, 2 lamy.*s) (src/inequality_helper.jl:144-158): the augmented diagonal
     next to the same couplings on the x half.  The diagonal ``dg`` is the caller's to set: it is allocated with the work vectors."""
-    from .projcg import BandedOperator, DiagonalsOperator, TridiagonalOperator
+    from .projcg import BandedOperator, DiagonalsOperator, SparseOperator, TridiagonalOperator
     if not hasattr(hess_lag_vec_, "diag_"):
         return None
     tri_off, band_off, diags_off = (getattr(hess_lag_vec_, name, None) for name in ("offdiag", "offdiags", "diagonals"))
@@ -130,6 +130,8 @@ def _coupled_operator(ctx, hess_lag_vec_):
         op = BandedOperator(0.0, None, band_off, band_off.m)
     elif diags_off is not None:
         op = DiagonalsOperator(0.0, None, diags_off[1], diags_off[0])
+    elif getattr(hess_lag_vec_, "sparse_hessian", None) is not None:
+        op = SparseOperator(0.0, None, hess_lag_vec_.sparse_hessian)
     else:
         return None
     op.fused = bool(getattr(ctx.options, "tridiagonal_one_pass", True))

@@ -273,6 +273,19 @@ def graph_diagonals(n: int, i, j, w):
     return diag, off, tuple(int(s) for s in dists)
 
 
+def grid_edges(shape, periodic=False, corners: bool = False):
+    """(i, j), i < j: the edges of the grid graph of a field of ``shape`` in row-major numbering, as two index arrays -- the edge list behind
+    :func:`grid_laplacian`, for :func:`graph_diagonals`, :class:`SparseHessian` and :class:`GraphSeparableLinear`.  ``periodic`` (a bool, or one
+    per axis) closes an axis on itself (it needs at least 3 points); ``corners`` joins every pair of points whose indices differ by at most 1
+    along every axis.  Any number of axes; no limit on the distances j - i that arise."""
+    shape = tuple(int(s) for s in shape)
+    per = (bool(periodic),) * len(shape) if np.ndim(periodic) == 0 else tuple(bool(p) for p in periodic)
+    assert len(per) == len(shape), "grid_edges: periodic is a bool or one bool per axis"
+    assert all(s >= 1 for s in shape) and int(np.prod(shape)) > 1, "grid_edges: a grid of more than one point"
+    assert all(s >= 3 for s, p in zip(shape, per) if p), "grid_edges: a periodic axis needs at least 3 points"
+    return _grid_edges(shape, per, bool(corners))
+
+
 def _grid_edges(shape, periodic, corners):
     """(i, j), i < j: the edges of the grid graph in row-major numbering.  Every offset in {-1, 0, 1}^d (corners) or along one axis whose first
     nonzero component is +1 names each edge once; a periodic axis wraps, any other drops the neighbours beyond its end."""
@@ -380,6 +393,67 @@ class GridSeparableLinear(SeparableLinearBallBox):
             deg2 = StackedVector(self.ctx, self.N)
             deg2.copy_range_from(self._deg, self.N)
             self._lap2 = DiagonalsOperator(0.0, deg2, self.diagonals[1], self.diagonals[0])
+            self._tmp2 = StackedVector(self.ctx, self.N)
+        return self._lap2.mul_(self._tmp2, x)
+
+    def f(self, x: DeviceVector) -> float:
+        from .device import dot
+        return super().f(x) + 0.5 * dot(x, self._smooth(x))
+
+    def grad_(self, g: DeviceVector, x: DeviceVector):
+        from .device import axpby
+        super().grad_(g, x)
+        axpby(1.0, self._smooth(x), 1.0, g)
+
+    def diag_objective_(self, hx: DeviceVector, x: DeviceVector):
+        from .device import axpby
+        super().diag_objective_(hx, x)
+        axpby(1.0, self._deg, 1.0, hx)
+
+    def diag_(self, hx: DeviceVector, x: DeviceVector, lam: np.ndarray):
+        from .device import axpby
+        super().diag_(hx, x, lam)
+        axpby(1.0, self._deg, 1.0, hx)
+
+
+class GraphSeparableLinear(SeparableLinearBallBox):
+    """A separable objective plus a smoothness term on an arbitrary GRAPH: f(x) = sum_i phi(x_i - c_i; a_i) + kappa/2 sum_e w_e (x_i - x_j)^2 over
+    the undirected edges ``edges = (i, j, w)`` (0-based index arrays, ``w`` a scalar or one weight per edge; repeated edges add up) -- a triangle
+    mesh, a k-nearest-neighbour graph, a grid in any numbering, at most 32 neighbours per vertex -- under dense linear equalities, with the optional
+    ball (slack variable) and box bounds of :class:`QuadLinearBallBox`.  The Lagrangian Hessian is a diagonal, phi''(x_i) + kappa (weighted degree)_i
+    (+ 2 lam_ball), plus the entries -kappa w_e: ``sparse_hessian`` below (a :class:`SparseHessian` of N rows; the slack row, when the ball is
+    there, has no couplings), and ``optimize`` hands it to projcg_ as a :class:`SparseOperator` -- the truncated-Newton solves keep one pass over the
+    basis per iteration (lfpsqp_projcg_sparse; with bounds the augmented stacked diagonal next to the same couplings).  One rank (the couplings
+    would cross the shard boundaries)."""
+
+    def __init__(self, ctx: Context, n: int, m: int, Jct: DeviceMatrix, b, kind: int, a, c=0.0, edges=None, kappa: float = 1.0, **kw):
+        assert kw.get("n_global", n) in (None, n), "graph objective: one rank (the couplings would cross the shard boundaries)"
+        assert edges is not None and len(edges) == 3, "graph objective: edges = (i, j, w)"
+        super().__init__(ctx, n, m, Jct, b, kind, a, c, **kw)
+        from .projcg import SparseHessian, SparseOperator
+        self.kappa = float(kappa)
+        N = self.N                                                        # n, or n + 1 with the ball's slack variable (no coupling to it)
+        ei, ej = (np.asarray(e, dtype=np.int64).ravel() for e in edges[:2])
+        assert ei.shape == ej.shape and np.all((0 <= ei) & (ei < n) & (0 <= ej) & (ej < n)), "graph objective: edges between the n variables"
+        w = self.kappa * np.broadcast_to(np.asarray(edges[2], dtype=np.float64), ei.shape)
+        deg = np.zeros(N)
+        deg[:n] = np.bincount(ei, w, n) + np.bincount(ej, w, n)
+        self._deg = ctx.vector(N, deg)
+        self.sparse_hessian = SparseHessian(ctx, N, ei, ej, -w)
+        self._lap = SparseOperator(0.0, self._deg, self.sparse_hessian)    # kappa L
+        self._tmp = ctx.vector(N)
+        self._lap2 = self._tmp2 = None                                    # the same over stacked iterates [x | gap | y] (bounds): zero on the y half
+
+    def _smooth(self, x: DeviceVector):
+        """tmp = kappa L x (x plain, or stacked: the x half)."""
+        if x.n == self.N:
+            return self._lap.mul_(self._tmp, x)
+        if self._lap2 is None:
+            from .inequality import StackedVector
+            from .projcg import SparseOperator
+            deg2 = StackedVector(self.ctx, self.N)
+            deg2.copy_range_from(self._deg, self.N)
+            self._lap2 = SparseOperator(0.0, deg2, self.sparse_hessian)
             self._tmp2 = StackedVector(self.ctx, self.N)
         return self._lap2.mul_(self._tmp2, x)
 

@@ -95,8 +95,8 @@ class LowRankOperator:
 
 
 class _CoupledOperator:
-    """A = a0*I + diag(dg) + symmetric off-diagonal couplings ``off``: what :class:`TridiagonalOperator`, :class:`BandedOperator` and
-    :class:`DiagonalsOperator` share.  A subclass supplies the two C calls: ``_mul`` (the operator on its own) and ``_solve`` (the fused ONE-pass
+    """A = a0*I + diag(dg) + symmetric off-diagonal couplings ``off``: what :class:`TridiagonalOperator`, :class:`BandedOperator`,
+    :class:`DiagonalsOperator` and :class:`SparseOperator` share.  A subclass supplies the two C calls: ``_mul`` (the operator on its own) and ``_solve`` (the fused ONE-pass
     projected CG; ``head`` and ``tail`` are the arguments before and after the operator's own).  ``fused = False`` sends projcg_ to the callback
     path (the generic loop / lfpsqp_projcg_op with ``mul_``: two passes over the basis per iteration)."""
 
@@ -202,6 +202,82 @@ class DiagonalsOperator(_CoupledOperator):
     def _solve(self, ctx, head, tail):
         solve = ctx.L.lfpsqp_projcg_stencil if self._wide else ctx.L.lfpsqp_projcg_diags
         return solve(*head, self.a0, self._dg_h(), self.off.h, len(self.dists), self._dist_c, *tail)
+
+
+class SparseHessian:
+    """The symmetric off-diagonal part S of a sparse Hessian A = a0*I + diag(dg) + S as a device handle (lfpsqp_sphess): built ONCE from the
+    undirected edge list ``(i, j, w)`` (0-based host arrays in any order, ``w`` a scalar or one value per edge: the entry A_ij = A_ji; duplicates
+    and mirrored duplicates add up), at most 32 entries per row.  The values are constant over the handle's lifetime.  ``n``, ``nedges`` (distinct
+    undirected edges), ``row_width`` (the largest row degree) and ``edge_width`` (the most edges one row owns: the number of set-up passes of a
+    one-pass solve) describe what was built.  The diagonal is not part of it: i == j raises."""
+
+    def __init__(self, ctx: Context, n: int, i, j, w):
+        import numpy as np
+        self.ctx = ctx
+        self.h = None
+        ii = np.ascontiguousarray(np.asarray(i, dtype=np.int64).ravel())
+        jj = np.ascontiguousarray(np.asarray(j, dtype=np.int64).ravel())
+        if ii.shape != jj.shape:
+            raise ValueError("SparseHessian: i and j of the same length")
+        ww = np.ascontiguousarray(np.broadcast_to(np.asarray(w, dtype=np.float64), ii.shape))
+        h = C.c_void_p()
+        ctx.check(ctx.L.lfpsqp_sphess_create(ctx.h, int(n), ii.size, ii.ctypes.data, jj.ctypes.data, ww.ctypes.data, C.byref(h)))
+        self.h = h
+        out = [_capi.c_i64() for _ in range(4)]
+        ctx.check(ctx.L.lfpsqp_sphess_info(self.h, *(C.byref(o) for o in out)))
+        self.n, self.nedges, self.row_width, self.edge_width = (o.value for o in out)
+
+    def close(self):
+        if self.h is not None:
+            self.ctx.L.lfpsqp_sphess_free(self.ctx.h, self.h)
+            self.h = None
+
+    free = close
+
+    def __del__(self):
+        try:
+            if getattr(self.ctx, "h", None) is not None:
+                self.close()
+        except Exception:
+            pass
+
+
+class SparseOperator(_CoupledOperator):
+    """(A v)_i = (a0 + dg_i) v_i + sum_{j in row i of S} S_ij v_j for a :class:`SparseHessian` ``S``: a diagonal Hessian plus couplings described by
+    ROW INDICES -- a smoothness term on a triangle mesh, a k-nearest-neighbour graph, a grid in any numbering, the 26-neighbour periodic 3-D stencil:
+    everything :class:`DiagonalsOperator` cannot express (more than 13 distinct distances j - i).  On a :class:`DeviceBasis` projcg_ runs it on the
+    fused ONE-pass iteration (lfpsqp_projcg_sparse); ``mul_`` is the operator on its own (lfpsqp_sphess_mul), which the generic loop /
+    lfpsqp_projcg_op use -- two passes over the basis per iteration.  ``fused = False`` sends projcg_ to that callback path.  With bounds (a stacked
+    basis): ``dg`` is a :class:`StackedVector` and ``S`` has N rows, the couplings of the x half, as for :class:`DiagonalsOperator`.
+
+    SET-UP COST.  The one-pass solve forms U'A U first: ``S.edge_width`` + 1 weighted Gram passes over the basis (+ 2 when A is not diagonally
+    dominant) whose operand gathers the partner rows, where the callback path has none; per iteration its two vector kernels move 12 bytes per
+    stored entry where the distance form moves 8 bytes per two.  Measured at (1e7, 128) on one MI355X (FINDINGS.md 19; ms per
+    iteration / set-up per solve): the 27-point stencil of 216^3 (row_width 26, edge_width 13) 3.92 / 79 against 4.27 / 4.4 on the callback
+    path -- break-even at 214 iterations per solve -- and 3.63 / 79 for :class:`DiagonalsOperator` on the same edges, which stays the form for
+    any graph with at most 13 distances; a triangulated 3200 x 3125 grid in row-major numbering (row_width 6, edge_width 3) 2.36 / 23 against
+    3.57 / 3.6, break-even at 16 iterations; the SAME mesh in a permuted numbering 5.28 / 101 against 4.51 / 4.7: without locality every
+    gathered value is a cache line of its own and the one-pass form LOSES per iteration and in the set-up -- use ``fused = False`` for a graph
+    whose numbering has no locality (and for short solves at large row_width).  ``tools/time_sphess.py GRID M [--corners | --mesh [--permute]]``
+    measures both paths for a given graph and says where the one-pass form never pays."""
+
+    def __init__(self, a0: float, dg: DeviceVector | None, S: SparseHessian):
+        if dg is not None and dg.ctx is not S.ctx:
+            raise ValueError("SparseOperator: the handle belongs to another context")
+        super().__init__(a0, dg, None)
+        self.S = S
+
+    def _check(self, ctx):
+        if ctx is not self.S.ctx:
+            raise ValueError("SparseOperator: the handle belongs to another context")
+
+    def _mul(self, ctx, v, out):
+        self._check(ctx)
+        return ctx.L.lfpsqp_sphess_mul(ctx.h, self.a0, self._dg_h(), self.S.h, v.h, out.h)
+
+    def _solve(self, ctx, head, tail):
+        self._check(ctx)
+        return ctx.L.lfpsqp_projcg_sparse(*head, self.a0, self._dg_h(), self.S.h, *tail)
 
 
 class DeviceBasis:
