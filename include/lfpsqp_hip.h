@@ -744,7 +744,11 @@ int lfpsqp_retract_nr_batch(lfpsqp_ctx* ctx, const lfpsqp_basis* U, const double
  * the reference's InequalityDecomp (src/inequality_helper.jl:215-271, fulljac at src/retractions.jl:324).
  * In: x = initial guess (the reference passes zeros), r = right-hand side.  Out: x, r = residual,
  * *flag = 1 iff *iters == maxiter (reference quirk :240-243), *iters.  p, z: n-vector work;
- * tmp_w: N-vector work (stacked only); tmp_m: >= ncols work. */
+ * tmp_w: N-vector work (stacked only); tmp_m: >= ncols work.
+ * The loop is the reference's `norm_res = Inf; while norm_res > tol && i < maxiter` (:202,207): an iteration runs only if
+ * maxiter > 0 AND Inf > tol.  With tol = +Inf or tol = NaN no iteration runs -- *iters = 0, *flag = 0, x and r untouched, p zero-filled
+ * (:204) -- exactly as with maxiter <= 0 (*flag = 1 for maxiter == 0).  A NaN residual norm ends the loop after the iteration that
+ * produced it (NaN > tol is false).  lfpsqp_pcg_pre has the same start and exit conditions. */
 int lfpsqp_pcg(lfpsqp_ctx* ctx, double mu, const lfpsqp_basis* Jop, lfpsqp_vec* x, lfpsqp_vec* r, lfpsqp_vec* p, lfpsqp_vec* z,
                lfpsqp_vec* tmp_w, lfpsqp_vec* tmp_m, double tol, int64_t maxiter, int* flag, int64_t* iters);
 
@@ -754,10 +758,15 @@ int lfpsqp_pcg(lfpsqp_ctx* ctx, double mu, const lfpsqp_basis* Jop, lfpsqp_vec* 
  * proj_precondition!(z, r, mu, U, Sigma, rank, tmp_m) (src/retractions.jl:248-257, the call commented out at :374); with K from the CURRENT
  * Jct the solve converges in one iteration (test/test_retractions.jl:126-139).  Two passes over Jct per iteration (lfpsqp_pcg: one; its
  * iteration counts on ill-conditioned bound problems run into the thousands).
- *   K   host, m x m column-major (symmetric)
+ *   K   host, m x m column-major, SYMMETRIC: entry j of K sP is formed from the m numbers stored at K + j m (column j), so a
+ *       non-symmetric matrix would be applied transposed
  *   i11, i12, i22   stacked operator only: the rows of D0^-1 = [i11 i12; i12 i22] (N-vectors); NULL for the plain operator (D0^-1 = 1/mu)
  *   q   work n-vector (A_f p)
- * Same outputs and exit semantics as lfpsqp_pcg.  LFPSQP_ERR_UNSUPPORTED without the one-pass kernels (sparse twin, m < 4 or > 1024). */
+ * Same outputs and exit semantics as lfpsqp_pcg.  LFPSQP_ERR_UNSUPPORTED without the one-pass kernels (sparse twin, m < 4 or > 1024);
+ * mu <= 0 (or NaN): LFPSQP_ERR_ARG.  A refused call leaves x, r, p, z and q untouched.
+ * With a stacked basis the call reads Jop->Dx, Jop->Dy (the a, b of D0's 2 x 2 blocks) and Jop->Z and SILENTLY IGNORES Jop->sx, Jop->sy
+ * (they must only be non-NULL): E = [Jct; 0] is the row scaling sx = 1, sy = 0, whatever the two vectors hold.  A caller with other
+ * row scalings gets the solve for (1, 0), not an error (tests/test_pcg_exact.py records this); use lfpsqp_pcg for the general form. */
 typedef struct lfpsqp_pcg_precond {
     const double* K;
     const lfpsqp_vec *i11, *i12, *i22;

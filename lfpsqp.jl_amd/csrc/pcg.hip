@@ -59,7 +59,7 @@ struct PInit {
         scal[P_TOL] = tol;
         istat[IP_ITER] = 0;
         istat[IP_MAXIT] = maxit;
-        const int64_t st = (maxit > 0) ? PST_RUNNING : PST_DONE;   // while norm_res > tol && i < maxiter, norm_res = Inf
+        const int64_t st = (maxit > 0 && INFINITY > tol) ? PST_RUNNING : PST_DONE;   // while norm_res > tol && i < maxiter, norm_res = Inf (:202,207): tol = Inf or NaN runs nothing
         istat[IP_STATUS] = st;
         hm.publish(st, 0);
     }
@@ -471,7 +471,7 @@ struct PrecInit {       // rho_prev = 1 (:203), status
         scal[P_TOL] = tol;
         istat[IP_ITER] = 0;
         istat[IP_MAXIT] = maxit;
-        const int64_t st = (maxit > 0) ? PST_RUNNING : PST_DONE;
+        const int64_t st = (maxit > 0 && INFINITY > tol) ? PST_RUNNING : PST_DONE;   // :202,207, as PInit
         istat[IP_STATUS] = st;
         hm.publish(st, 0);
     }

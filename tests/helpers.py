@@ -4,7 +4,7 @@ from fractions import Fraction
 import numpy as np
 
 # ---- shared by the exact-reference suites (tests/test_primitives_exact.py, tests/test_matrix_cores_exact.py,
-#      tests/test_constraints_exact.py) ------------------------------------------------------------------------------------------------
+#      tests/test_constraints_exact.py, tests/test_pcg_exact.py) ---------------------------------------------------------------------
 U = 2.0 ** -53                                   # unit roundoff of binary64
 POISON = -1.2345678912345e+77                    # (a value no operation here produces)
 
