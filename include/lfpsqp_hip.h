@@ -548,8 +548,8 @@ int lfpsqp_stencil_mul(lfpsqp_ctx* ctx, double a0, const lfpsqp_vec* dg, const l
  * lfpsqp_sphess_create builds the handle ONCE from host triplets (0-based, any order): a triplet (i, j, v), i != j, adds v to BOTH A_ij and A_ji;
  * duplicates add up, (j, i) counting as a duplicate of (i, j); a position whose duplicates sum to zero keeps its slot.  LFPSQP_ERR_ARG: i == j (the
  * diagonal is dg's job), an index outside [0, n), a non-finite value.  LFPSQP_ERR_UNSUPPORTED: a row with more than 32 distinct neighbours after
- * merging (32 is accepted), n >= 2^31 (indices are stored as int32).  The values are constant over the handle's lifetime: the x-dependent part of
- * a Lagrangian Hessian arrives through dg, as for every coupled kind.
+ * merging (32 is accepted), n >= 2^31 (indices are stored as int32).  The values stay as created unless lfpsqp_sphess_edge_eval (below) rewrites them; the
+ * x-dependent DIAGONAL part of a Lagrangian Hessian arrives through dg, as for every coupled kind.
  * Two ELL forms on the device (slot k: one int32 index array and one double array of padded length -- consecutive rows of a slot are coalesced):
  *   by rows (row_width = the largest row degree): a row's neighbours in increasing index order, which fixes the summation order of the products,
  *     (A v)_i = fma chain over the row's slots in slot order, starting from (a0 + dg_i) v_i; an empty slot holds the row itself and 0.0;
@@ -573,6 +573,31 @@ int lfpsqp_sphess_mul(lfpsqp_ctx* ctx, double a0, const lfpsqp_vec* dg, const lf
 int lfpsqp_projcg_sparse(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, double a0, const lfpsqp_vec* dg, const lfpsqp_sphess* S, lfpsqp_vec* Av,
                          const lfpsqp_basis* U, const lfpsqp_vec* b, const lfpsqp_vec* c, double tol, int64_t maxit, int64_t n_global, int flags,
                          const lfpsqp_projcg_work* work, int64_t* iters, double* nr);
+
+/* VALUES THAT CHANGE WITH x: a non-quadratic edge term  scale * sum_e w_e psi(x_i - x_j)  over the undirected edges of a handle -- edge-preserving
+ * (pseudo-Huber) smoothing on a mesh or a k-nearest-neighbour graph, a stiffening quartic -- whose Hessian has the handle's pattern and the
+ * off-diagonal values -(scale w_e) psi''(x_i - x_j).  Rebuilding a handle per outer iteration sorts on the host; these two entries keep it on the device.
+ * lfpsqp_sphess_like: *out = a second handle on W's PATTERN.  The index arrays of both forms are shared, not copied (a reference count: the handles
+ * may be freed in either order, each with lfpsqp_sphess_free; the pattern goes with the last one); the value arrays are its own, initialised to
+ * W's values.  lfpsqp_sphess_info reports the same four numbers for both; every entry that takes a handle takes it.
+ * lfpsqp_sphess_edge_eval: W holds the edge weights w_e as created and is never written.  The first W.n entries of x are the variables (a stacked
+ * iterate or a slack entry behind them is not read).  With t = x_i - x_j per undirected edge (i, j):
+ *     *f         = scale * sum_e w_e psi(t)                          (each edge once: the row form's sum, halved -- exact)
+ *     grad_i    += scale * sum_{j ~ i} w_ij psi'(x_i - x_j)          (i < W.n; a row's terms in slot order, one fma each, then one fma with scale)
+ *     diag_i    += scale * sum_{j ~ i} w_ij psi''(x_i - x_j)         (i < W.n)
+ *     H's value at every stored edge, in BOTH forms, = -(scale w_e) psi''(t)
+ * entries >= W.n of grad and diag are untouched; any of f, grad, diag and H may be NULL (f alone: a kernel that writes no vector).
+ *     kind 0: psi = t^2/2            kind 1: psi = t^2/2 + t^4/4            kind 2: psi = t^2 / (sqrt(1 + u^2) + 1), u = t / delta
+ * (kind 2 is the pseudo-Huber function delta^2 (sqrt(1 + u^2) - 1) in the form without cancellation that lfpsqp_separable uses; psi' =
+ * t / sqrt(1 + u^2), psi'' = 1 / ((1 + u^2) sqrt(1 + u^2)); delta is ignored by the other kinds).  psi'' is computed from t*t alone, so both
+ * endpoints of an edge and both forms store the same bits; with kind 0 the stored value is exactly -(scale w_e), what lfpsqp_sphess_create
+ * stores for the triplet value -(scale w_e).  The energy is summed by the library's two-stage fixed-order reduction: bit-reproducible per handle.
+ * H must be a handle made by lfpsqp_sphess_like on W's pattern (or by _like of such a handle); H == W is refused: W would lose the weights.
+ * LFPSQP_ERR_ARG: kind outside 0 .. 2; kind 2 with delta not finite or <= 0; scale not finite; x shorter than W.n; grad or diag shorter than W.n,
+ * aliasing x or each other; H on another pattern or H == W.  LFPSQP_ERR_UNSUPPORTED: a communicator, as for lfpsqp_sphess_mul. */
+int lfpsqp_sphess_like(lfpsqp_ctx* ctx, const lfpsqp_sphess* W, lfpsqp_sphess** out);
+int lfpsqp_sphess_edge_eval(lfpsqp_ctx* ctx, const lfpsqp_sphess* W, int kind, double delta, double scale, const lfpsqp_vec* x, double* f,
+                            lfpsqp_vec* grad, lfpsqp_vec* diag, lfpsqp_sphess* H);
 
 /* The same solver for a GENERAL symmetric operator A -- the reference's LinearMap closure around hess_lag_vec! /
  * augmented_hess_lag_vec! (src/optimize.jl:228-230, applied at src/projcg.jl:57,74,116): `A(user, src, dest)` must produce

@@ -253,6 +253,8 @@ c_sphess_create(ctx, n, nnz, rows, cols, vals, out) = ccall((:lfpsqp_sphess_crea
 c_sphess_free(ctx, S) = ccall((:lfpsqp_sphess_free, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), ctx, S)
 c_sphess_info(S, n, nedges, kr, ke) = ccall((:lfpsqp_sphess_info, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}), S, n, nedges, kr, ke)
 c_sphess_mul(ctx, a0, dg, S, v, out) = ccall((:lfpsqp_sphess_mul, lib), Cint, (Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), ctx, a0, dg, S, v, out)
+c_sphess_like(ctx, W, out) = ccall((:lfpsqp_sphess_like, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}), ctx, W, out)
+c_sphess_edge_eval(ctx, W, kind, delta, scale, x, f, grad, diag, H) = ccall((:lfpsqp_sphess_edge_eval, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Float64, Float64, Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), ctx, W, kind, delta, scale, x, f, grad, diag, H)
 c_projcg_sparse(ctx, x, lam, a0, dg, S, Av, U, b, c, tol, maxit, nglob, flags, work, iters, nr) = ccall((:lfpsqp_projcg_sparse, lib), Cint,
     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{CBasis}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Int64, Int64, Cint, Ref{CWork}, Ref{Int64}, Ref{Float64}),
     ctx, x, lam, a0, dg, S, Av, U, b, c, tol, maxit, nglob, flags, work, iters, nr)
@@ -645,7 +647,8 @@ function LinearAlgebra.mul!(dest::DeviceVector, A::DiagonalsOperator, v::DeviceV
 end
 
 # The symmetric off-diagonal part of a sparse Hessian (lfpsqp_sphess), from 1-based undirected edges (I[e], J[e]) with the entries V[e] = A_ij =
-# A_ji: any order, duplicates and mirrored duplicates add up, at most 32 entries per row; the values are constant over the handle's lifetime.
+# A_ji: any order, duplicates and mirrored duplicates add up, at most 32 entries per row; the values stay as built unless the handle is the `out` of
+# edge_eval!, which rewrites them on the device (a handle made by `like`: the same pattern, its own values).
 mutable struct SparseHessian
     ctx::HipContext
     h::Ptr{Cvoid}
@@ -663,6 +666,24 @@ function SparseHessian(ctx::HipContext, n::Integer, I::Vector{Int}, J::Vector{In
     S = SparseHessian(ctx, r[], Int(nn[]), Int(ne[]), Int(kr[]), Int(ke[]))
     finalizer(x -> c_sphess_free(x.ctx.h, x.h), S)
     return S
+end
+# A second handle on the same pattern (lfpsqp_sphess_like): the index arrays are shared, the values are its own, initialised to W's; either may
+# be finalised first.
+function like(W::SparseHessian)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    check(W.ctx, c_sphess_like(W.ctx.h, W.h, r))
+    H = SparseHessian(W.ctx, r[], W.n, W.nedges, W.row_width, W.edge_width)
+    finalizer(x -> c_sphess_free(x.ctx.h, x.h), H)
+    return H
+end
+# The edge term scale Σ_e w_e ψ(x_i - x_j) with W's values as the weights (lfpsqp_sphess_edge_eval; kind 0: t²/2, 1: t²/2 + t⁴/4, 2: pseudo-Huber
+# with scale delta): returns its value (nothing with want_f = false), ADDS its gradient to `grad` and scale Σ_j w_ij ψ'' to `diag` (the first W.n
+# entries; x may be longer, a stacked iterate) and writes the values -(scale w_e) ψ'' into `out`, a handle made by `like`.  W is never modified.
+function edge_eval!(W::SparseHessian, kind::Integer, delta::Float64, scale::Float64, x::DeviceVector; grad=nothing, diag=nothing, out=nothing, want_f::Bool=true)
+    f = Ref{Float64}(0.0)
+    check(W.ctx, c_sphess_edge_eval(W.ctx.h, W.h, Cint(kind), delta, scale, x.h, want_f ? f : Ptr{Float64}(C_NULL),
+                                    grad === nothing ? C_NULL : grad.h, diag === nothing ? C_NULL : diag.h, out === nothing ? C_NULL : out.h))
+    return want_f ? f[] : nothing
 end
 # (A v)_i = (a0 + dg_i) v_i + Σ_{j in row i of S} S_ij v_j: a diagonal Hessian plus couplings described by row indices (a mesh, a k-nearest-neighbour
 # graph, a grid in any numbering: what DiagonalsOperator cannot express).  projcg! keeps ONE pass over the basis per iteration with it
@@ -2016,6 +2037,55 @@ function optimize(P::ChainSeparableLinear, x0::Vector{Float64}, param::LFPSQPPar
     return x[1:B.n], obj, λ, info
 end
 
+# ---- separable objective plus a NON-QUADRATIC edge term on a graph: f(x) = Σ φ(x_i - c_i; a_i) + κ Σ_e w_e ψ(x_i - x_j; δ) -------------------------
+# over the 1-based undirected edges (I[e], J[e]) with weights w[e]; edge_kind 0: ψ = t²/2, 1: t²/2 + t⁴/4, 2: pseudo-Huber with scale δ.  The
+# Lagrangian Hessian has the graph's pattern and values that change with x: the diagonal φ''(x_i) + κ Σ_j w_ij ψ''(x_i - x_j) and the entries
+# -κ w_e ψ''(x_i - x_j).  `weights` holds w (never modified), `hess` = like(weights) the current entries: hess_diag! / hess_diag_objective! --
+# optimize_core calls one of them at the current x before every truncated-Newton solve -- add the diagonal and rewrite `hess` in the same device
+# call, and optimize_core finds it through hess_sparse (lfpsqp_projcg_sparse).  One rank, no ball, no bounds, as ChainSeparableLinear.
+struct GraphPotentialLinear
+    sep::SeparableLinearBallBox
+    κ::Float64
+    edge_kind::Int
+    δ::Float64
+    weights::SparseHessian
+    hess::SparseHessian
+end
+function GraphPotentialLinear(ctx::HipContext, n::Int, m::Int, Jct::DeviceMatrix, b::Vector{Float64}, kind::Int, a::Vector{Float64}, c::Vector{Float64},
+                              I::Vector{Int}, J::Vector{Int}, w::Vector{Float64}; κ::Float64=1.0, edge_kind::Int=2, δ::Float64=1.0)
+    ctx.nranks == 1 || error("graph objective: one rank (the couplings would cross the shard boundaries)")
+    0 <= edge_kind <= 2 || error("graph objective: edge_kind 0 .. 2")
+    sep = SeparableLinearBallBox(ctx, n, m, Jct, b, kind, a, c)
+    weights = SparseHessian(ctx, n, I, J, w)
+    return GraphPotentialLinear(sep, κ, edge_kind, δ, weights, like(weights))
+end
+function objective(P::GraphPotentialLinear, x::DeviceVector)
+    return objective(P.sep, x) + edge_eval!(P.weights, P.edge_kind, P.δ, P.κ, x)
+end
+function gradient!(P::GraphPotentialLinear, g::DeviceVector, x::DeviceVector)
+    gradient!(P.sep, g, x)
+    edge_eval!(P.weights, P.edge_kind, P.δ, P.κ, x; grad=g, want_f=false)
+    return g
+end
+function hess_diag!(P::GraphPotentialLinear, hx::DeviceVector, x::DeviceVector, λ::Vector{Float64})
+    hess_diag!(P.sep, hx, x, λ)
+    edge_eval!(P.weights, P.edge_kind, P.δ, P.κ, x; diag=hx, out=P.hess, want_f=false)
+    return hx
+end
+function hess_diag_objective!(P::GraphPotentialLinear, hx::DeviceVector, x::DeviceVector)
+    hess_diag_objective!(P.sep, hx, x)
+    edge_eval!(P.weights, P.edge_kind, P.δ, P.κ, x; diag=hx, out=P.hess, want_f=false)
+    return hx
+end
+hess_constraints(P::GraphPotentialLinear) = P.sep.base.cons
+hess_sparse(P::GraphPotentialLinear) = P.hess
+function optimize(P::GraphPotentialLinear, x0::Vector{Float64}, param::LFPSQPParams=LFPSQPParams())
+    B = P.sep.base
+    x, obj, λ, info = optimize_core(B.ctx, x -> objective(P, x), (g, x) -> gradient!(P, g, x), B.cons, (J, cv, x) -> jac!(B.cons, J, cv, x), P,
+                                    x0, nothing, nothing, B.m, param; n_global=B.n_global)
+    return x[1:B.n], obj, λ, info
+end
+
 # ---- device-resident class with NONLINEAR equalities: separable objective under ElementwiseConstraints, optional box bounds ----------
 struct SeparableElementwiseBox
     ctx::HipContext
@@ -2114,7 +2184,7 @@ optimize(ctx::HipContext, f, grad!, c!, jac_c!, d!, jac_d!, hess_lag_vec!, x0::V
 
 export HipContext, HipError, DeviceOptions, DeviceVector, StackedVector, DeviceMatrix, SparseMatrix, spmv_t!, spmv_n!, to_dense!, DeviceBasis, DiagOperator, LowRankOperator, InequalityData, InequalityDecomp,
        InequalityDecompProject, ProjCGWork, DeviceConstraints, NR, ProjPenalty, ProjPenaltyWork, Euclidean, YRetract, ArmijoWork,
-       ExactLinesearchWork, LFPSQPParams, TerminationInfo, QuadLinearBallBox, SeparableLinearBallBox, ChainSeparableLinear, TridiagonalOperator, BandedOperator, DiagonalsOperator, SparseHessian, SparseOperator, SeparableElementwiseBox, ElementwiseConstraints,
+       ExactLinesearchWork, LFPSQPParams, TerminationInfo, QuadLinearBallBox, SeparableLinearBallBox, ChainSeparableLinear, GraphPotentialLinear, like, edge_eval!, TridiagonalOperator, BandedOperator, DiagonalsOperator, SparseHessian, SparseOperator, SeparableElementwiseBox, ElementwiseConstraints,
        sin_system_constraints, sphere_system_constraints, clone, rowscale!, set_placement!, basis_and_vectors_placed, vectors_placed, placement_info, upload!, download, upload2!, download2, projcg!, retract!,
        retract_nr_batch!, pcg!, ProjPrecondition, ksvd!, armijo!, exact_linesearch!, optimize, optimize_core, hess_diag!, jac!, comm_unique_id, comm_init!, comm_p2p_export, comm_init_p2p!,
        shard_range, sync

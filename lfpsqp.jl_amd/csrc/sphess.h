@@ -7,6 +7,7 @@
 //   by ROWS  (Kr slots): the neighbours of row i in increasing index order -- the products; an empty slot holds i itself and 0.0;
 //   by EDGES (Ke slots): every undirected edge once, at its owner -- the set-up of the reduced operator; an empty slot holds i and 0.0.
 // Pad rows (n .. npad - 1) hold the index 0 and 0.0.
+// Handles made by lfpsqp_sphess_like share the two index arrays (the PATTERN) and own their value arrays: the pattern is freed with the last of them.
 struct lfpsqp_sphess {
     int64_t n = 0, nedges = 0;
     int Kr = 0, Ke = 0;
@@ -15,6 +16,7 @@ struct lfpsqp_sphess {
     double* rval = nullptr;
     int32_t* eidx = nullptr;        // [max(Ke, 1)][npad]
     double* eval = nullptr;
+    mutable int* pattern_refs = nullptr;   // host counter of the handles on ridx / eidx; nullptr: this handle alone (never shared)
 };
 
 namespace lfpsqp {

@@ -100,9 +100,39 @@ int lfpsqp_sphess_create(lfpsqp_ctx* ctx, int64_t n, int64_t nnz, const int64_t*
 int lfpsqp_sphess_free(lfpsqp_ctx* ctx, lfpsqp_sphess* S) {
     if (!S) return 0;
     if (ctx) (void)hipStreamSynchronize(ctx->stream);
-    for (void* p : {(void*)S->ridx, (void*)S->rval, (void*)S->eidx, (void*)S->eval})
+    bool last = true;                                   // the pattern goes with the last handle on it
+    if (S->pattern_refs) {
+        last = --*S->pattern_refs == 0;
+        if (last) delete S->pattern_refs;
+    }
+    for (void* p : {last ? (void*)S->ridx : nullptr, (void*)S->rval, last ? (void*)S->eidx : nullptr, (void*)S->eval})
         if (p) (void)hipFree(p);
     delete S;
+    return 0;
+}
+
+int lfpsqp_sphess_like(lfpsqp_ctx* ctx, const lfpsqp_sphess* W, lfpsqp_sphess** out) {
+    LF_ARG(ctx, ctx && W && out);
+    *out = nullptr;
+    lfpsqp_sphess* H = new lfpsqp_sphess(*W);
+    H->rval = H->eval = nullptr;
+    H->pattern_refs = nullptr;                          // (until the copies stand: freeing H then leaves W's pattern alone)
+    H->ridx = H->eidx = nullptr;
+    const size_t npad = (size_t)W->npad, rsz = (size_t)std::max(W->Kr, 1) * npad, esz = (size_t)std::max(W->Ke, 1) * npad;
+    bool ok = hipMalloc((void**)&H->rval, rsz * sizeof(double)) == hipSuccess && hipMalloc((void**)&H->eval, esz * sizeof(double)) == hipSuccess;
+    if (ok) ok = hipMemcpyAsync(H->rval, W->rval, rsz * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream) == hipSuccess;
+    if (ok) ok = hipMemcpyAsync(H->eval, W->eval, esz * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream) == hipSuccess;
+    if (ok) ok = hipStreamSynchronize(ctx->stream) == hipSuccess;
+    if (!ok) {
+        lfpsqp_sphess_free(ctx, H);
+        return set_err(ctx, LFPSQP_ERR_HIP, "sphess: device allocation / copy failed");
+    }
+    if (!W->pattern_refs) W->pattern_refs = new int(1);
+    ++*W->pattern_refs;
+    H->pattern_refs = W->pattern_refs;
+    H->ridx = W->ridx;
+    H->eidx = W->eidx;
+    *out = H;
     return 0;
 }
 

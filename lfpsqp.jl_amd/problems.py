@@ -477,6 +477,52 @@ class GraphSeparableLinear(SeparableLinearBallBox):
         axpby(1.0, self._deg, 1.0, hx)
 
 
+class GraphPotentialLinear(SeparableLinearBallBox):
+    """A separable objective plus a NON-QUADRATIC edge term on a graph: f(x) = sum_i phi(x_i - c_i; a_i) + kappa sum_e w_e psi(x_i - x_j; delta) over
+    the undirected edges ``edges = (i, j, w)`` of :class:`GraphSeparableLinear` -- ``edge_kind`` 0: psi = t^2/2 (that class's term), 1: t^2/2 +
+    t^4/4 (stiffening), 2: the pseudo-Huber function delta^2 (sqrt(1 + (t/delta)^2) - 1) (edge-preserving smoothing) -- under the same constraint
+    set (dense linear equalities, optional ball with its slack row, optional box).  The Lagrangian Hessian has the graph's pattern and values that
+    CHANGE with x: the diagonal phi''(x_i) + kappa sum_j w_ij psi''(x_i - x_j) (+ 2 lam_ball) and the entries -kappa w_e psi''(x_i - x_j).
+    ``weights`` holds w (a :class:`SparseHessian` of N rows, never modified) and ``sparse_hessian`` = ``weights.like()`` the current entries:
+    ``diag_objective_`` / ``diag_`` -- ``optimize`` calls one of them at the current x before every truncated-Newton solve -- add the diagonal
+    and rewrite ``sparse_hessian`` in the same device call (lfpsqp_sphess_edge_eval), so ``optimize`` runs it as a :class:`SparseOperator` on
+    lfpsqp_projcg_sparse exactly as it runs the constant class; f is the kernel that only reads.  One rank.  For a graph whose numbering has no
+    locality set ``ctx.options.tridiagonal_one_pass = False`` (``SparseOperator.fused = False``), as FINDINGS.md 19 advises for the constant
+    class: the gathers of the solve, and of this evaluation, then fetch a cache line per value either way."""
+
+    def __init__(self, ctx: Context, n: int, m: int, Jct: DeviceMatrix, b, kind: int, a, c=0.0, edges=None, kappa: float = 1.0, edge_kind: int = 2,
+                 delta: float = 1.0, **kw):
+        assert kw.get("n_global", n) in (None, n), "graph objective: one rank (the couplings would cross the shard boundaries)"
+        assert edges is not None and len(edges) == 3, "graph objective: edges = (i, j, w)"
+        assert int(edge_kind) in (0, 1, 2), "graph objective: edge_kind 0 .. 2"
+        super().__init__(ctx, n, m, Jct, b, kind, a, c, **kw)
+        from .projcg import SparseHessian
+        self.kappa, self.edge_kind, self.delta = float(kappa), int(edge_kind), float(delta)
+        ei, ej = (np.asarray(e, dtype=np.int64).ravel() for e in edges[:2])
+        assert ei.shape == ej.shape and np.all((0 <= ei) & (ei < n) & (0 <= ej) & (ej < n)), "graph objective: edges between the n variables"
+        w = np.broadcast_to(np.asarray(edges[2], dtype=np.float64), ei.shape)
+        self.weights = SparseHessian(ctx, self.N, ei, ej, w)             # N rows: the slack row, when the ball is there, has no edges
+        self.sparse_hessian = self.weights.like()
+
+    def _edge(self, x, grad=None, diag=None, out=None, want_f=False):
+        return self.weights.edge_eval(self.edge_kind, self.delta, self.kappa, x, grad, diag, out, want_f)
+
+    def f(self, x: DeviceVector) -> float:
+        return super().f(x) + self._edge(x, want_f=True)
+
+    def grad_(self, g: DeviceVector, x: DeviceVector):
+        super().grad_(g, x)
+        self._edge(x, grad=g)
+
+    def diag_objective_(self, hx: DeviceVector, x: DeviceVector):
+        super().diag_objective_(hx, x)
+        self._edge(x, diag=hx, out=self.sparse_hessian)
+
+    def diag_(self, hx: DeviceVector, x: DeviceVector, lam: np.ndarray):
+        super().diag_(hx, x, lam)
+        self._edge(x, diag=hx, out=self.sparse_hessian)
+
+
 class SeparableElementwiseBox(SeparableLinearBallBox):
     """The device-resident problem class with NONLINEAR equality constraints: a separable objective
     (``kind`` / ``a`` / ``c`` as in :class:`SeparableLinearBallBox`) under ``cons``, an :class:`ElementwiseConstraints`

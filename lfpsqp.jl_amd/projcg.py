@@ -207,7 +207,8 @@ class DiagonalsOperator(_CoupledOperator):
 class SparseHessian:
     """The symmetric off-diagonal part S of a sparse Hessian A = a0*I + diag(dg) + S as a device handle (lfpsqp_sphess): built ONCE from the
     undirected edge list ``(i, j, w)`` (0-based host arrays in any order, ``w`` a scalar or one value per edge: the entry A_ij = A_ji; duplicates
-    and mirrored duplicates add up), at most 32 entries per row.  The values are constant over the handle's lifetime.  ``n``, ``nedges`` (distinct
+    and mirrored duplicates add up), at most 32 entries per row.  The values stay as built unless the handle is the ``out`` of :meth:`edge_eval`, which rewrites them on the device (a
+    handle made by :meth:`like`: the same pattern, its own values).  ``n``, ``nedges`` (distinct
     undirected edges), ``row_width`` (the largest row degree) and ``edge_width`` (the most edges one row owns: the number of set-up passes of a
     one-pass solve) describe what was built.  The diagonal is not part of it: i == j raises."""
 
@@ -226,6 +227,34 @@ class SparseHessian:
         out = [_capi.c_i64() for _ in range(4)]
         ctx.check(ctx.L.lfpsqp_sphess_info(self.h, *(C.byref(o) for o in out)))
         self.n, self.nedges, self.row_width, self.edge_width = (o.value for o in out)
+
+    def like(self) -> "SparseHessian":
+        """A second handle on the same pattern (lfpsqp_sphess_like): the index arrays are shared, the values are its own, initialised to this
+        handle's.  The two may be closed in either order."""
+        ctx = self.ctx
+        h = C.c_void_p()
+        ctx.check(ctx.L.lfpsqp_sphess_like(ctx.h, self.h, C.byref(h)))
+        H = object.__new__(SparseHessian)
+        H.ctx, H.h = ctx, h
+        out = [_capi.c_i64() for _ in range(4)]
+        ctx.check(ctx.L.lfpsqp_sphess_info(H.h, *(C.byref(o) for o in out)))
+        H.n, H.nedges, H.row_width, H.edge_width = (o.value for o in out)
+        return H
+
+    def edge_eval(self, kind: int, delta: float, scale: float, x, grad=None, diag=None, out=None, want_f: bool = True):
+        """The edge term scale * sum_e w_e psi(x_i - x_j) with this handle's values as the weights w_e (lfpsqp_sphess_edge_eval; ``kind`` 0:
+        t^2/2, 1: t^2/2 + t^4/4, 2: pseudo-Huber with scale ``delta``): returns its value (None with ``want_f=False``: no reduction is run),
+        ADDS its gradient to ``grad`` and scale * sum_j w_ij psi'' to ``diag`` (the first ``n`` entries of either; ``x`` may be longer, a stacked
+        iterate: its first ``n`` entries are read) and writes the off-diagonal values -(scale w_e) psi'' into ``out``, a handle made by
+        :meth:`like`.  With nothing but the value asked for, the kernel writes no vector.  This handle is never modified."""
+        ctx = self.ctx
+        if out is not None and out.ctx is not ctx:
+            raise ValueError("SparseHessian.edge_eval: the output handle belongs to another context")
+        f = C.c_double()
+        ctx.check(ctx.L.lfpsqp_sphess_edge_eval(ctx.h, self.h, int(kind), float(delta), float(scale), x.h, C.byref(f) if want_f else None,
+                                                grad.h if grad is not None else None, diag.h if diag is not None else None,
+                                                out.h if out is not None else None))
+        return f.value if want_f else None
 
     def close(self):
         if self.h is not None:
