@@ -599,6 +599,35 @@ int lfpsqp_sphess_like(lfpsqp_ctx* ctx, const lfpsqp_sphess* W, lfpsqp_sphess** 
 int lfpsqp_sphess_edge_eval(lfpsqp_ctx* ctx, const lfpsqp_sphess* W, int kind, double delta, double scale, const lfpsqp_vec* x, double* f,
                             lfpsqp_vec* grad, lfpsqp_vec* diag, lfpsqp_sphess* H);
 
+/* VALUES SUPPLIED BY THE CALLER on a fixed pattern: the structure / values contract of a sparse NLP interface (declare the Hessian's structure
+ * once, fill an array of values per iteration) for a Lagrangian Hessian that lfpsqp_sphess_edge_eval cannot express.
+ * lfpsqp_sphess_map_create: built ONCE on the host from nnz triplet positions (rows, cols) (0-based, any order) against the pattern of S, and
+ * uploaded.  The convention is that of lfpsqp_sphess_create: a triplet p with rows[p] != cols[p] contributes vals[p] to BOTH A_ij and A_ji, (j, i)
+ * counts as a duplicate of (i, j), duplicates add up in the order given.  New here: triplets with rows[p] == cols[p] are allowed; they form the
+ * DIAGONAL output.  Every off-diagonal triplet must be an edge of S's pattern (LFPSQP_ERR_ARG, the entry named in lfpsqp_last_error); an edge of
+ * the pattern that no triplet names gets the value +0.0.  LFPSQP_ERR_ARG: an index outside [0, S.n).  LFPSQP_ERR_UNSUPPORTED: nnz >= 2^31
+ * (positions are stored as int32).  The map holds a reference on S's pattern through the counter of lfpsqp_sphess_like: the map and the handles
+ * may be freed in any order (the map with lfpsqp_sphess_map_free).  S's index arrays are read back from the device for the build.
+ * On the device (all int32): per slot of the row form and of the edge form, and per row for the diagonal, the position of its FIRST triplet or
+ * -1; and, only when some position is named more than once, next[nnz]: the position of the next duplicate in the order given, or -1.
+ * lfpsqp_sphess_map_info: nnz, ndiag (the triplets on the diagonal) and max_dup (the longest chain of duplicates; 1 without duplicates, 0 for
+ * nnz = 0); any output may be NULL.
+ * lfpsqp_sphess_set_values: vals is a device vector of at least nnz entries; H any handle on the map's pattern -- S itself or a handle made by
+ * lfpsqp_sphess_like (no handle holds weights here that must be kept).  Every stored slot of BOTH forms of H becomes the chain sum
+ * ((v_p0 + v_p1) + v_p2) ... of its triplets in the order given -- the sum starts from the first value, not from zero -- or +0.0 without one:
+ * exactly what lfpsqp_sphess_create computes for the same triplets, so a refreshed handle is bit for bit a freshly created one and the two forms
+ * of an edge hold the same bits.  diag[i], i < S.n, = the chain sum of row i's diagonal triplets, +0.0 without one: diag is OVERWRITTEN, not added
+ * to; entries >= S.n (a stacked vector, a slack row behind) are untouched.  Either of diag and H may be NULL.  The values are NOT checked for
+ * finiteness on the device: a caller that cannot vouch for them checks on the host before the upload.  Two vector kernels (20 bytes per stored
+ * slot of either form, 20 more per row), vector stores only.
+ * LFPSQP_ERR_ARG: vals shorter than nnz; diag shorter than S.n or aliasing vals; H on another pattern.  LFPSQP_ERR_UNSUPPORTED: a communicator, as
+ * for lfpsqp_sphess_mul. */
+typedef struct lfpsqp_sphess_map lfpsqp_sphess_map;
+int lfpsqp_sphess_map_create(lfpsqp_ctx* ctx, const lfpsqp_sphess* S, int64_t nnz, const int64_t* rows, const int64_t* cols, lfpsqp_sphess_map** out);
+int lfpsqp_sphess_map_free(lfpsqp_ctx* ctx, lfpsqp_sphess_map* M);
+int lfpsqp_sphess_map_info(const lfpsqp_sphess_map* M, int64_t* nnz, int64_t* ndiag, int64_t* max_dup);
+int lfpsqp_sphess_set_values(lfpsqp_ctx* ctx, const lfpsqp_sphess_map* M, const lfpsqp_vec* vals, lfpsqp_vec* diag, lfpsqp_sphess* H);
+
 /* The same solver for a GENERAL symmetric operator A -- the reference's LinearMap closure around hess_lag_vec! /
  * augmented_hess_lag_vec! (src/optimize.jl:228-230, applied at src/projcg.jl:57,74,116): `A(user, src, dest)` must produce
  * dest = A * src for device vectors of length(b) (stacked [x | gap | y] when U is a stacked basis), return 0, and leave

@@ -249,6 +249,10 @@ c_projcg_stencil(ctx, x, lam, a0, dg, off, K, dist, Av, U, b, c, tol, maxit, ngl
     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Cvoid}, Ref{CBasis}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Int64, Int64, Cint, Ref{CWork}, Ref{Int64}, Ref{Float64}),
     ctx, x, lam, a0, dg, off, K, dist, Av, U, b, c, tol, maxit, nglob, flags, work, iters, nr)
 c_stencil_mul(ctx, a0, dg, off, K, dist, v, out) = ccall((:lfpsqp_stencil_mul, lib), Cint, (Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Cvoid}, Ptr{Cvoid}), ctx, a0, dg, off, K, dist, v, out)
+c_sphess_map_create(ctx, S, nnz, rows, cols, out) = ccall((:lfpsqp_sphess_map_create, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Ref{Ptr{Cvoid}}), ctx, S, nnz, rows, cols, out)
+c_sphess_map_free(ctx, M) = ccall((:lfpsqp_sphess_map_free, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), ctx, M)
+c_sphess_map_info(M, nnz, ndiag, max_dup) = ccall((:lfpsqp_sphess_map_info, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}), M, nnz, ndiag, max_dup)
+c_sphess_set_values(ctx, M, vals, diag, H) = ccall((:lfpsqp_sphess_set_values, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), ctx, M, vals, diag, H)
 c_sphess_create(ctx, n, nnz, rows, cols, vals, out) = ccall((:lfpsqp_sphess_create, lib), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ref{Ptr{Cvoid}}), ctx, n, nnz, rows, cols, vals, out)
 c_sphess_free(ctx, S) = ccall((:lfpsqp_sphess_free, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), ctx, S)
 c_sphess_info(S, n, nedges, kr, ke) = ccall((:lfpsqp_sphess_info, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}), S, n, nedges, kr, ke)
@@ -684,6 +688,34 @@ function edge_eval!(W::SparseHessian, kind::Integer, delta::Float64, scale::Floa
     check(W.ctx, c_sphess_edge_eval(W.ctx.h, W.h, Cint(kind), delta, scale, x.h, want_f ? f : Ptr{Float64}(C_NULL),
                                     grad === nothing ? C_NULL : grad.h, diag === nothing ? C_NULL : diag.h, out === nothing ? C_NULL : out.h))
     return want_f ? f[] : nothing
+end
+# The structure / values interface (lfpsqp_sphess_map): 1-based triplet positions (I[p], J[p]) declared ONCE against the pattern of S -- the
+# convention of SparseHessian (a triplet counts for A_ij and A_ji, duplicates and mirrored duplicates add up in the order given), and I[p] == J[p]
+# is allowed: those triplets form the diagonal.  Every off-diagonal triplet must be an edge of S.  The map holds a reference on the pattern: it
+# and the handles may be finalised in any order.
+mutable struct SparsePattern
+    ctx::HipContext
+    h::Ptr{Cvoid}
+    nnz::Int
+    ndiag::Int
+    max_dup::Int
+end
+function SparsePattern(S::SparseHessian, I::Vector{Int}, J::Vector{Int})
+    length(I) == length(J) || error("I and J are of different lengths")
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    check(S.ctx, c_sphess_map_create(S.ctx.h, S.h, Int64(length(I)), Int64.(I .- 1), Int64.(J .- 1), r))
+    nz = Ref{Int64}(0); nd = Ref{Int64}(0); md = Ref{Int64}(0)
+    check(S.ctx, c_sphess_map_info(r[], nz, nd, md))
+    M = SparsePattern(S.ctx, r[], Int(nz[]), Int(nd[]), Int(md[]))
+    finalizer(x -> c_sphess_map_free(x.ctx.h, x.h), M)
+    return M
+end
+# vals (a device vector of at least M.nnz entries) placed into both forms of `out` (any handle on the map's pattern) and into `diag` (its first n
+# entries OVERWRITTEN with the sums of the diagonal triplets, 0 where a row has none): lfpsqp_sphess_set_values.  The stored value of an edge is the
+# sum of its triplets in the order given: what SparseHessian builds from the same triplets, bit for bit.  Values are not checked for finiteness.
+function set_values!(M::SparsePattern, vals::DeviceVector; diag=nothing, out=nothing)
+    check(M.ctx, c_sphess_set_values(M.ctx.h, M.h, vals.h, diag === nothing ? C_NULL : diag.h, out === nothing ? C_NULL : out.h))
+    return nothing
 end
 # (A v)_i = (a0 + dg_i) v_i + Σ_{j in row i of S} S_ij v_j: a diagonal Hessian plus couplings described by row indices (a mesh, a k-nearest-neighbour
 # graph, a grid in any numbering: what DiagonalsOperator cannot express).  projcg! keeps ONE pass over the basis per iteration with it
@@ -2184,7 +2216,7 @@ optimize(ctx::HipContext, f, grad!, c!, jac_c!, d!, jac_d!, hess_lag_vec!, x0::V
 
 export HipContext, HipError, DeviceOptions, DeviceVector, StackedVector, DeviceMatrix, SparseMatrix, spmv_t!, spmv_n!, to_dense!, DeviceBasis, DiagOperator, LowRankOperator, InequalityData, InequalityDecomp,
        InequalityDecompProject, ProjCGWork, DeviceConstraints, NR, ProjPenalty, ProjPenaltyWork, Euclidean, YRetract, ArmijoWork,
-       ExactLinesearchWork, LFPSQPParams, TerminationInfo, QuadLinearBallBox, SeparableLinearBallBox, ChainSeparableLinear, GraphPotentialLinear, like, edge_eval!, TridiagonalOperator, BandedOperator, DiagonalsOperator, SparseHessian, SparseOperator, SeparableElementwiseBox, ElementwiseConstraints,
+       ExactLinesearchWork, LFPSQPParams, TerminationInfo, QuadLinearBallBox, SeparableLinearBallBox, ChainSeparableLinear, GraphPotentialLinear, like, edge_eval!, SparsePattern, set_values!, TridiagonalOperator, BandedOperator, DiagonalsOperator, SparseHessian, SparseOperator, SeparableElementwiseBox, ElementwiseConstraints,
        sin_system_constraints, sphere_system_constraints, clone, rowscale!, set_placement!, basis_and_vectors_placed, vectors_placed, placement_info, upload!, download, upload2!, download2, projcg!, retract!,
        retract_nr_batch!, pcg!, ProjPrecondition, ksvd!, armijo!, exact_linesearch!, optimize, optimize_core, hess_diag!, jac!, comm_unique_id, comm_init!, comm_p2p_export, comm_init_p2p!,
        shard_range, sync

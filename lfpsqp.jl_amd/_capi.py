@@ -188,6 +188,10 @@ _SIGS = {
     "lfpsqp_sphess_mul": [P, c_dbl, P, P, P, P],
     "lfpsqp_sphess_like": [P, P, C.POINTER(P)],
     "lfpsqp_sphess_edge_eval": [P, P, C.c_int, c_dbl, c_dbl, P, PD, P, P, P],
+    "lfpsqp_sphess_map_create": [P, P, c_i64, P, P, C.POINTER(P)],
+    "lfpsqp_sphess_map_free": [P, P],
+    "lfpsqp_sphess_map_info": [P, C.POINTER(c_i64), C.POINTER(c_i64), C.POINTER(c_i64)],
+    "lfpsqp_sphess_set_values": [P, P, P, P, P],
     "lfpsqp_projcg_sparse": [P, P, P, c_dbl, P, P, P, C.POINTER(Basis), P, P, c_dbl, c_i64, c_i64, C.c_int,
                              C.POINTER(ProjCGWorkC), C.POINTER(c_i64), PD],
     "lfpsqp_projcg_op": [P, P, P, P, P, P, C.POINTER(Basis), P, P, c_dbl, c_i64, c_i64, C.c_int,

@@ -11,8 +11,10 @@ outer iteration.  Callback contract (the device analogue of the reference's):
     c_                        DeviceConstraints, or a host callable c_(cval, x_host)
     jac_(Jct, cval, x)        refreshes the device n x m matrix Jct (= Jc' of the reference) and cval
     hess_lag_vec_             either an object with ``diag_(hx, x, lam)`` filling the N-vector hx with
-                              the diagonal of the Lagrangian Hessian (fused projcg path), or a callable
-                              hess_lag_vec_(dest, src, x, lam) on device vectors (generic path)
+                              the diagonal of the Lagrangian Hessian (fused projcg path; with couplings next
+                              to it, see _coupled_operator -- problems.SparseLagrangianHessian arrives here as
+                              such an object), or a callable hess_lag_vec_(dest, src, x, lam) on device vectors
+                              (generic path)
 
 Deviations from the reference, all invisible in the iterates up to rounding: the thin SVD is the
 Gram-based factorisation of lfpsqp_factorize (basis rotation / sign freedom; the rank is the reference's
@@ -341,7 +343,11 @@ def optimize_core(f, grad_, c_, jac_, hess_lag_vec_, x0, xl, xu, m: int, param: 
                     th[:rank] = Wgen[:, :rank].T @ Jtd
                     th[:rank] /= S_[:rank]
                     lam_kkt[:] = Vt_.T @ th
-                    hess_lag_vec_.diag_(hdst, x, lam_kkt)
+                    # (a class whose diag_ is a HOST call -- ``host_values``: the pattern form of problems.py -- is not asked on an iteration
+                    # already known to end below, :347-355: no solve will read the diagonal the pass completes)
+                    ending = f_diff <= param.eps_f or step_diff <= param.eps_x or i >= param.maxiter
+                    if not (ending and getattr(hess_lag_vec_, "host_values", False)):
+                        hess_lag_vec_.diag_(hdst, x, lam_kkt)
                     cc = None
                 wc = projcgwork._c()
                 sig_c = np.ascontiguousarray(S_, dtype=np.float64)

@@ -558,9 +558,73 @@ class Derivatives:
     """Analytic derivatives in the user's variables (the reference gets them by AD,
     src/autodiff_generators.jl -- out of scope).  All callables take HOST arrays."""
     grad_: Callable
-    hess_lag_vec_: Callable
+    hess_lag_vec_: Optional[Callable]
     jac_c_: Optional[Callable] = None
     jac_d_: Optional[Callable] = None
+    # a sparse Lagrangian Hessian on a fixed pattern (:class:`SparseLagrangianHessian`): ``hess_pattern = (rows, cols)`` with
+    # ``hess_values_(vals, x, lam)``; ``hess_lag_vec_`` may then be None
+    hess_pattern: Optional[tuple] = None
+    hess_values_: Optional[Callable] = None
+
+
+class SparseLagrangianHessian:
+    """The structure / values interface for the Lagrangian Hessian (Ipopt's ``eval_h``, JuMP, CasADi): the triplet pattern ``(rows, cols)``
+    (0-based host arrays) is declared ONCE; ``values_(vals, x, lam)`` fills the host array ``vals`` of ``nnz`` entries with the triplet values of
+    the Hessian of the Lagrangian at the host arrays ``(x, lam)`` -- lam's sign as in the reference's ``hess_lag_vec!(dest, src, x, lam)``:
+    dest = (hess f(x) + sum_k lam_k hess c_k(x)) src.  Triangle convention of :class:`SparseHessian`: a triplet with rows != cols counts for
+    A_ij AND A_ji (a caller holding a full symmetric matrix passes one triangle), (j, i) is a duplicate of (i, j), duplicates add up in the order
+    given; triplets with rows == cols form the diagonal.  At most 32 distinct neighbours per row: more raises the library's error.
+
+    Accepted as ``hess_lag_vec!`` by the 9-argument ``optimize`` and through ``Derivatives(..., hess_pattern=, hess_values_=)``: before every
+    truncated-Newton solve ``values_`` is called ONCE, the values are uploaded and placed into a :class:`SparseHessian` and the Hessian diagonal by
+    one device call (lfpsqp_sphess_set_values), and the solve runs a :class:`SparseOperator` -- on lfpsqp_projcg_sparse, or with
+    ``ctx.options.tridiagonal_one_pass = False`` on the device callback path over lfpsqp_sphess_mul -- with nothing n-sized crossing PCIe inside
+    it.  Non-finite values raise ValueError."""
+
+    def __init__(self, rows, cols, values_):
+        self.rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).ravel())
+        self.cols = np.ascontiguousarray(np.asarray(cols, dtype=np.int64).ravel())
+        if self.rows.shape != self.cols.shape:
+            raise ValueError("SparseLagrangianHessian: rows and cols of the same length")
+        if not callable(values_):
+            raise TypeError("SparseLagrangianHessian: values_(vals, x, lam) must be callable")
+        self.values_ = values_
+        self.nnz = int(self.rows.size)
+
+
+class _SparsePatternHessian:
+    """A :class:`SparseLagrangianHessian` in the protocol ``optimize_core`` knows: ``diag_(hx, x, lam)`` next to ``sparse_hessian``.  ``n`` rows
+    on the device (slack rows included: they have no triplets, so their diagonal is 0); ``values_`` sees the first ``nx`` entries of x.
+    ``host_values`` tells the driver that ``diag_`` costs a host call: it is not made on an outer iteration already known to be the last."""
+
+    host_values = True
+
+    def __init__(self, ctx, n, nx, hess):
+        from .projcg import SparseHessian
+        if hess.nnz and (min(hess.rows.min(), hess.cols.min()) < 0 or max(hess.rows.max(), hess.cols.max()) >= nx):
+            raise ValueError("SparseLagrangianHessian: a triplet outside the variables")
+        self.n, self.nx, self.values_ = n, nx, hess.values_
+        self.sparse_hessian, self.pattern = SparseHessian.from_pattern(ctx, n, hess.rows, hess.cols)
+        self.vals = np.zeros(hess.nnz)
+
+    def diag_(self, hx: DeviceVector, x: DeviceVector, lam: np.ndarray):
+        self.values_(self.vals, x.download(self.nx, 0), lam)
+        if not np.all(np.isfinite(self.vals)):
+            raise ValueError("SparseLagrangianHessian: values_ produced a non-finite value")
+        self.pattern.set_values(self.vals, diag=hx, out=self.sparse_hessian)
+
+    def close(self):
+        self.pattern.close()
+        self.sparse_hessian.close()
+
+
+def _hessian_of(dv):
+    """What a Derivatives object says about the Lagrangian Hessian: the pattern form when given, else the matrix-free callable."""
+    if dv.hess_pattern is None and dv.hess_values_ is None:
+        return dv.hess_lag_vec_
+    if dv.hess_pattern is None or dv.hess_values_ is None or len(dv.hess_pattern) != 2:
+        raise ValueError("Derivatives: hess_pattern = (rows, cols) goes with hess_values_")
+    return SparseLagrangianHessian(dv.hess_pattern[0], dv.hess_pattern[1], dv.hess_values_)
 
 
 def optimize(*args, derivatives: Optional[Derivatives] = None, ctx: Optional[Context] = None, trace=None):
@@ -583,13 +647,13 @@ def optimize(*args, derivatives: Optional[Derivatives] = None, ctx: Optional[Con
     dv = derivatives
     if k == 2:
         f, x0 = args
-        return _host_core(ctx, f, dv.grad_, None, None, dv.hess_lag_vec_, x0, None, None, 0, param, trace)
+        return _host_core(ctx, f, dv.grad_, None, None, _hessian_of(dv), x0, None, None, 0, param, trace)
     if k == 4:
         f, c_, x0, m = args
-        return _host_core(ctx, f, dv.grad_, c_, dv.jac_c_, dv.hess_lag_vec_, x0, None, None, m, param, trace)
+        return _host_core(ctx, f, dv.grad_, c_, dv.jac_c_, _hessian_of(dv), x0, None, None, m, param, trace)
     if k == 6:
         f, c_, x0, xl, xu, m = args
-        return _host_core(ctx, f, dv.grad_, c_, dv.jac_c_ if m > 0 else None, dv.hess_lag_vec_, x0, xl, xu, m, param, trace)
+        return _host_core(ctx, f, dv.grad_, c_, dv.jac_c_ if m > 0 else None, _hessian_of(dv), x0, xl, xu, m, param, trace)
     if k == 8:      # (f, c!, d!, x0, xl, xu, m, p)   d <= 0                         src/optimize.jl:83
         f, c_, d_, x0, xl, xu, m, p = args
         return _host_slack(ctx, f, c_, d_, -np.inf * np.ones(p), np.zeros(p), x0, xl, xu, m, p, param, dv, trace)
@@ -637,17 +701,22 @@ def _host_slack(ctx, f, c_, d_, dl, du, x0, xl, xu, m, p, param, dv, trace):
         cval[m:m + p] -= x[n:n + p]
         J[m:m + p, n:n + p] = -np.eye(p)
 
-    def hlv_aux_(dest, src, x, lam):
-        dv.hess_lag_vec_(dest[:n], src[:n], x[:n], lam)
-        dest[n:] = 0.0
+    hess = _hessian_of(dv)
+    if isinstance(hess, SparseLagrangianHessian):    # the same pattern over n + p rows (the slack rows have no triplets); values_ sees x[:n]
+        hlv_aux_ = hess
+    else:
+        def hlv_aux_(dest, src, x, lam):
+            hess(dest[:n], src[:n], x[:n], lam)
+            dest[n:] = 0.0
 
-    x, obj, lam, ti = _host_core(ctx, f_aux, grad_aux_, c_aux_, jac_aux_, hlv_aux_, x0_aux, xl_aux, xu_aux, m + p, param, trace)
+    x, obj, lam, ti = _host_core(ctx, f_aux, grad_aux_, c_aux_, jac_aux_, hlv_aux_, x0_aux, xl_aux, xu_aux, m + p, param, trace, nx=n)
     return x[:n], obj, lam, ti
 
 
-def _host_core(ctx, f, grad_, c_, jac_, hlv_, x0, xl, xu, m, param, trace):
+def _host_core(ctx, f, grad_, c_, jac_, hlv_, x0, xl, xu, m, param, trace, nx=None):
     """Adapters: host callables -> the device-vector contract of optimize_core (no bounds + general
-    Hessian: generic projcg path)."""
+    Hessian: generic projcg path; a :class:`SparseLagrangianHessian`: a SparseOperator refreshed on the device, ``nx`` the variables its
+    ``values_`` sees when slack rows follow them)."""
     x0 = np.asarray(x0, dtype=np.float64)
     n = len(x0)
 
@@ -669,4 +738,10 @@ def _host_core(ctx, f, grad_, c_, jac_, hlv_, x0, xl, xu, m, param, trace):
         hlv_(out, src.download(n, 0), x.download(n, 0), lam.download(max(m, 1))[:m])
         dest.upload(out, 0)
 
+    if isinstance(hlv_, SparseLagrangianHessian):
+        hess = _SparsePatternHessian(ctx, n, n if nx is None else nx, hlv_)
+        try:
+            return optimize_core(f_dev, grad_dev, c_, jac_dev if m > 0 else None, hess, x0, xl, xu, m, param, ctx=ctx, trace=trace)
+        finally:
+            hess.close()
     return optimize_core(f_dev, grad_dev, c_, jac_dev if m > 0 else None, hlv_dev, x0, xl, xu, m, param, ctx=ctx, trace=trace)

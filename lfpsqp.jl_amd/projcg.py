@@ -256,10 +256,90 @@ class SparseHessian:
                                                 out.h if out is not None else None))
         return f.value if want_f else None
 
+    @classmethod
+    def from_pattern(cls, ctx: Context, n: int, rows, cols):
+        """``(S, pattern)`` for the structure / values interface: ``S`` a handle over the off-diagonal triplets of ``(rows, cols)`` (0-based, the
+        edge-list convention of the constructor; triplets with rows == cols are dropped for the handle) created with zero values, and
+        ``pattern`` the :class:`SparsePattern` over the FULL triplet list, diagonal included, whose :meth:`SparsePattern.set_values` fills ``S`` (or
+        any handle made by :meth:`like`) and a diagonal vector from ``nnz`` values."""
+        import numpy as np
+        rr = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).ravel())
+        cc = np.ascontiguousarray(np.asarray(cols, dtype=np.int64).ravel())
+        if rr.shape != cc.shape:
+            raise ValueError("SparseHessian.from_pattern: rows and cols of the same length")
+        off = rr != cc
+        S = cls(ctx, n, rr[off], cc[off], 0.0)
+        try:
+            return S, SparsePattern(S, rr, cc)
+        except Exception:
+            S.close()
+            raise
+
     def close(self):
         if self.h is not None:
             self.ctx.L.lfpsqp_sphess_free(self.ctx.h, self.h)
             self.h = None
+
+    free = close
+
+    def __del__(self):
+        try:
+            if getattr(self.ctx, "h", None) is not None:
+                self.close()
+        except Exception:
+            pass
+
+
+class SparsePattern:
+    """A triplet pattern ``(rows, cols)`` declared ONCE against the pattern of a :class:`SparseHessian` ``S`` (lfpsqp_sphess_map): the convention is
+    the constructor's -- a triplet counts for A_ij and A_ji, duplicates and mirrored duplicates add up in the order given -- and rows == cols is
+    allowed: those triplets form the diagonal.  Every off-diagonal triplet must be an edge of ``S`` (the library's error names the entry).  ``nnz``,
+    ``ndiag`` (triplets on the diagonal) and ``max_dup`` (the longest chain of duplicates) describe what was declared.  The map holds a reference
+    on the pattern: it and the handles may be closed in any order."""
+
+    def __init__(self, S: SparseHessian, rows, cols):
+        import numpy as np
+        self.ctx = ctx = S.ctx
+        self.h = None
+        self._vals = None
+        rr = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).ravel())
+        cc = np.ascontiguousarray(np.asarray(cols, dtype=np.int64).ravel())
+        if rr.shape != cc.shape:
+            raise ValueError("SparsePattern: rows and cols of the same length")
+        h = C.c_void_p()
+        ctx.check(ctx.L.lfpsqp_sphess_map_create(ctx.h, S.h, rr.size, rr.ctypes.data, cc.ctypes.data, C.byref(h)))
+        self.h = h
+        out = [_capi.c_i64() for _ in range(3)]
+        ctx.check(ctx.L.lfpsqp_sphess_map_info(self.h, *(C.byref(o) for o in out)))
+        self.nnz, self.ndiag, self.max_dup = (o.value for o in out)
+
+    def set_values(self, vals, diag=None, out=None):
+        """``vals`` -- a :class:`DeviceVector` of at least ``nnz`` entries, or a host array, uploaded into a vector this object keeps -- placed into
+        both forms of ``out`` (any handle on the pattern) and into ``diag`` (lfpsqp_sphess_set_values): a stored value is the sum of its triplets in
+        the order given, the bits :class:`SparseHessian` builds from the same triplets; the first ``n`` entries of ``diag`` are OVERWRITTEN with the
+        sums of the diagonal triplets (0 where a row has none), entries behind them are left alone.  Values are not checked for finiteness."""
+        ctx = self.ctx
+        if out is not None and out.ctx is not ctx:
+            raise ValueError("SparsePattern.set_values: the output handle belongs to another context")
+        if not isinstance(vals, DeviceVector):
+            import numpy as np
+            vh = np.ascontiguousarray(np.asarray(vals, dtype=np.float64).ravel())
+            if vh.size < self.nnz:
+                raise ValueError(f"SparsePattern.set_values: {vh.size} values for {self.nnz} triplets")
+            if self._vals is None:
+                self._vals = DeviceVector(ctx, max(self.nnz, 1))
+            if self.nnz > 0:
+                self._vals.upload(vh[:self.nnz])
+            vals = self._vals
+        ctx.check(ctx.L.lfpsqp_sphess_set_values(ctx.h, self.h, vals.h, diag.h if diag is not None else None, out.h if out is not None else None))
+
+    def close(self):
+        if self.h is not None:
+            self.ctx.L.lfpsqp_sphess_map_free(self.ctx.h, self.h)
+            self.h = None
+        if self._vals is not None:
+            self._vals.free()
+            self._vals = None
 
     free = close
 
