@@ -23,41 +23,37 @@ int set_err(lfpsqp_ctx* ctx, int code, const char* fmt, ...) {
     return code;
 }
 
+// the grow step the scratch buffers share -- a rare, synchronising event (first call at a new size): drain the stream, free, allocate `cap`
+// doubles (zero-filled on request)
+static int regrow(lfpsqp_ctx* ctx, double** buf, size_t* have, size_t cap, bool zero) {
+    LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (*buf) LF_HIP(ctx, hipFree(*buf));
+    *buf = nullptr;
+    *have = 0;
+    LF_HIP(ctx, hipMalloc((void**)buf, cap * sizeof(double)));
+    if (zero) LF_HIP(ctx, hipMemsetAsync(*buf, 0, cap * sizeof(double), ctx->stream));
+    *have = cap;
+    return 0;
+}
+
 int ensure_part(lfpsqp_ctx* ctx, size_t doubles) {
     if (doubles <= ctx->part_cap) return 0;
-    // growing the workspace is a rare, synchronising event (first call at a new size)
-    LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->part) LF_HIP(ctx, hipFree(ctx->part));
-    ctx->part = nullptr;
-    ctx->part_cap = 0;
-    size_t cap = doubles + doubles / 4 + 4096;
-    LF_HIP(ctx, hipMalloc((void**)&ctx->part, cap * sizeof(double)));
-    ctx->part_cap = cap;
-    return 0;
+    return regrow(ctx, &ctx->part, &ctx->part_cap, doubles + doubles / 4 + 4096, false);
 }
 
 int ensure_small(lfpsqp_ctx* ctx, size_t doubles) {
     if (doubles <= ctx->small_cap) return 0;
-    LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->small) LF_HIP(ctx, hipFree(ctx->small));
-    ctx->small = nullptr;
-    ctx->small_cap = 0;
-    LF_HIP(ctx, hipMalloc((void**)&ctx->small, doubles * sizeof(double)));
-    ctx->small_cap = doubles;
-    return 0;
+    return regrow(ctx, &ctx->small, &ctx->small_cap, doubles, false);
+}
+
+int ensure_tri(lfpsqp_ctx* ctx, size_t doubles) {
+    if (doubles <= ctx->tri_cap) return 0;
+    return regrow(ctx, &ctx->d_tri, &ctx->tri_cap, doubles, false);
 }
 
 int ensure_nvec(lfpsqp_ctx* ctx, size_t doubles) {
     if (doubles <= ctx->nvec_cap) return 0;
-    LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_nvec) LF_HIP(ctx, hipFree(ctx->d_nvec));
-    ctx->d_nvec = nullptr;
-    ctx->nvec_cap = 0;
-    const size_t cap = (size_t)round_up((int64_t)doubles + 1, kPadRows);
-    LF_HIP(ctx, hipMalloc((void**)&ctx->d_nvec, cap * sizeof(double)));
-    LF_HIP(ctx, hipMemsetAsync(ctx->d_nvec, 0, cap * sizeof(double), ctx->stream));
-    ctx->nvec_cap = cap;
-    return 0;
+    return regrow(ctx, &ctx->d_nvec, &ctx->nvec_cap, (size_t)round_up((int64_t)doubles + 1, kPadRows), true);
 }
 
 int ensure_view(lfpsqp_ctx* ctx) {
@@ -97,12 +93,11 @@ int ensure_mvec(lfpsqp_ctx* ctx, size_t doubles) {
     ctx->pcg_resume.valid = false;        // whoever asks for the m-vector staging area is about to overwrite it
     if (doubles <= ctx->m_cap) return 0;
     LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_m) LF_HIP(ctx, hipFree(ctx->d_m));
     if (ctx->h_m) LF_HIP(ctx, hipHostFree(ctx->h_m));
-    ctx->d_m = nullptr; ctx->h_m = nullptr; ctx->m_cap = 0;
-    const size_t cap = (size_t)round_up((int64_t)doubles + 64, kPadRows);
-    LF_HIP(ctx, hipMalloc((void**)&ctx->d_m, cap * sizeof(double)));
-    LF_HIP(ctx, hipMemsetAsync(ctx->d_m, 0, cap * sizeof(double), ctx->stream));
+    ctx->h_m = nullptr;
+    size_t cap = ctx->m_cap;
+    ctx->m_cap = 0;                       // (d_m and its pinned mirror h_m share the capacity: set once both exist)
+    LF_TRY(regrow(ctx, &ctx->d_m, &cap, (size_t)round_up((int64_t)doubles + 64, kPadRows), true));
     LF_HIP(ctx, hipHostMalloc((void**)&ctx->h_m, cap * sizeof(double)));
     LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->m_cap = cap;

@@ -674,6 +674,18 @@ struct SqrtWTimesV {
     }
 };
 
+// d_nvec as gram_impl and its view form share it: [a view's combined weights | the square roots of the weights (| two columns in scaled space)],
+// each npad = round_up(n + 1, kPadRows) long
+struct GramNvec { size_t wts, sqrtw, col[2], size; };
+static GramNvec gram_nvec(int64_t n, bool cols) {
+    const size_t npad = (size_t)round_up(n + 1, kPadRows);
+    Layout L;
+    GramNvec s{L.skip(npad), L.skip(npad), {0, 0}, 0};
+    if (cols) { s.col[0] = L.skip(npad); s.col[1] = L.skip(npad); }
+    s.size = L.size();
+    return s;
+}
+
 static int gram_impl(lfpsqp_ctx* ctx, const lfpsqp_mat* M, int ncols_all, const double* w2, std::vector<double>& G, const GramRhs* rhs = nullptr,
                      const double* shift_sgn = nullptr, int64_t shift = 1, const int32_t* gather = nullptr) {
     // gather != NULL (with shift_sgn): R_i = M_i + shift_sgn_i M_{gather[i]} (gram_kernel SHIFT = -2; `shift` is not used)
@@ -691,19 +703,19 @@ static int gram_impl(lfpsqp_ctx* ctx, const lfpsqp_mat* M, int ncols_all, const 
         // weights rs^2 w2: sgn(rs) sqrt(w2) u), as do the caller's own columns (sgn(rs) e_k, plus w (u' sqrt(w2) e_k) for the rank-one term); one
         // dot-product kernel, assembled on the host
         const lfpsqp_mat plain = M->plain();
-        const size_t npad = (size_t)round_up(M->n + 1, kPadRows);
-        LF_TRY(ensure_nvec(ctx, 4 * npad));       // [combined weights | their square roots (the plain call below) | two columns in scaled space]
+        const GramNvec nv = gram_nvec(M->n, true);      // (the square roots: the plain call below)
+        LF_TRY(ensure_nvec(ctx, nv.size));
         const double* wts = w2;
         if (M->rs) {
-            LF_TRY((run_vec<ViewWeightF, 0, NoPost>(ctx, M->n, ViewWeightF{M->rs, w2, ctx->d_nvec}, 0u, nullptr, NoPost())));
-            wts = ctx->d_nvec;
+            LF_TRY((run_vec<ViewWeightF, 0, NoPost>(ctx, M->n, ViewWeightF{M->rs, w2, ctx->d_nvec + nv.wts}, 0u, nullptr, NoPost())));
+            wts = ctx->d_nvec + nv.wts;
         }
         GramRhs inner;
         std::vector<double> Xin;
         inner.X = &Xin;
         for (int k = 0; k < nxu; ++k) {
             if (!M->rs) { inner.e[inner.nx++] = rhs->e[k]; continue; }
-            double* dst = ctx->d_nvec + (2 + inner.nx) * npad;
+            double* dst = ctx->d_nvec + nv.col[inner.nx];
             LF_TRY((run_vec<SignScaleF, 0, NoPost>(ctx, M->n, SignScaleF{rhs->e[k], M->rs, nullptr, dst}, 0u, nullptr, NoPost())));
             inner.e[inner.nx++] = dst;
         }
@@ -711,7 +723,7 @@ static int gram_impl(lfpsqp_ctx* ctx, const lfpsqp_mat* M, int ncols_all, const 
         if (z_rides) {
             if (!M->rs && !w2) inner.e[inner.nx++] = M->ru;
             else {
-                double* dst = ctx->d_nvec + (2 + inner.nx) * npad;
+                double* dst = ctx->d_nvec + nv.col[inner.nx];
                 LF_TRY((run_vec<SignScaleF, 0, NoPost>(ctx, M->n, SignScaleF{M->ru, M->rs, w2, dst}, 0u, nullptr, NoPost())));
                 inner.e[inner.nx++] = dst;
             }
@@ -722,23 +734,27 @@ static int gram_impl(lfpsqp_ctx* ctx, const lfpsqp_mat* M, int ncols_all, const 
             for (int k = 0; k < nxu; ++k)
                 for (int i = 0; i < mm; ++i) (*rhs->X)[(size_t)k * mm + i] = Xin[(size_t)k * mm + i];
         if (!M->ru) return 0;
-        LF_TRY(ensure_mvec(ctx, (size_t)2 * mm + 16));
-        double* dz = ctx->d_m;                                   // [z (mm) ; u' W2 u ; w (mm) ; u' sqrt(W2) e_k (2)] -> host
-        if (!z_rides) LF_TRY(run_gemv_t(ctx, &plain, mm, M->n, ViewRank1V{M->rs, w2, M->ru}, dz));
-        LF_TRY((run_vec<ViewRank1DotF, 1, NoPost>(ctx, M->n, ViewRank1DotF{w2, M->ru}, 0u, dz + mm, NoPost())));
-        LF_HIP(ctx, hipMemcpyAsync(dz + mm + 1, M->rw, sizeof(double) * mm, hipMemcpyDeviceToDevice, ctx->stream));
+        Layout L;                                                // d_m, read back through h_m as one block
+        const size_t oz = L.skip(mm, 1), ouu = L.skip(1, 1), ow = L.skip(mm, 1), oue = L.skip(2, 1);  // [z ; u' W2 u ; w ; u' sqrt(W2) e_k]
+        const size_t nback = L.size();
+        L.skip(13, 1);                                           // tail: purpose unknown; kept
+        LF_TRY(ensure_mvec(ctx, L.size()));
+        double* dz = ctx->d_m;
+        if (!z_rides) LF_TRY(run_gemv_t(ctx, &plain, mm, M->n, ViewRank1V{M->rs, w2, M->ru}, dz + oz));
+        LF_TRY((run_vec<ViewRank1DotF, 1, NoPost>(ctx, M->n, ViewRank1DotF{w2, M->ru}, 0u, dz + ouu, NoPost())));
+        LF_HIP(ctx, hipMemcpyAsync(dz + ow, M->rw, sizeof(double) * mm, hipMemcpyDeviceToDevice, ctx->stream));
         if (nxu > 0)
-            LF_TRY((run_vec<ViewRhsDotF, 2, NoPost>(ctx, M->n, ViewRhsDotF{M->ru, w2, rhs->e[0], nxu > 1 ? rhs->e[1] : nullptr}, 0u, dz + 2 * mm + 1, NoPost())));
-        LF_HIP(ctx, hipMemcpyAsync(ctx->h_m, dz, sizeof(double) * (2 * mm + 3), hipMemcpyDeviceToHost, ctx->stream));
+            LF_TRY((run_vec<ViewRhsDotF, 2, NoPost>(ctx, M->n, ViewRhsDotF{M->ru, w2, rhs->e[0], nxu > 1 ? rhs->e[1] : nullptr}, 0u, dz + oue, NoPost())));
+        LF_HIP(ctx, hipMemcpyAsync(ctx->h_m, dz, sizeof(double) * nback, hipMemcpyDeviceToHost, ctx->stream));
         LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        const double* z = z_rides ? &Xin[(size_t)(inner.nx - 1) * mm] : ctx->h_m;
-        const double uu = ctx->h_m[mm];
-        const double* w = ctx->h_m + mm + 1;
+        const double* z = z_rides ? &Xin[(size_t)(inner.nx - 1) * mm] : ctx->h_m + oz;
+        const double uu = ctx->h_m[ouu];
+        const double* w = ctx->h_m + ow;
         for (int jj = 0; jj < mm; ++jj)
             for (int ii = 0; ii < mm; ++ii) G[(size_t)jj * mm + ii] += z[ii] * w[jj] + w[ii] * z[jj] + uu * w[ii] * w[jj];
         if (rhs && rhs->X)
             for (int k = 0; k < nxu; ++k)
-                for (int i = 0; i < mm; ++i) (*rhs->X)[(size_t)k * mm + i] += w[i] * ctx->h_m[2 * mm + 1 + k];
+                for (int i = 0; i < mm; ++i) (*rhs->X)[(size_t)k * mm + i] += w[i] * ctx->h_m[oue + k];
         return 0;
     }
     // A few columns beyond a multiple of the 128-column panel (m + 1 constraints with a slack/ball column, say) would cost
@@ -775,17 +791,17 @@ static int gram_impl(lfpsqp_ctx* ctx, const lfpsqp_mat* M, int ncols_all, const 
     const int64_t tile2 = (int64_t)kPanel * kPanel;
     const double* exs[2] = {nxu > 0 ? rhs->e[0] : nullptr, nxu > 1 ? rhs->e[1] : nullptr};
     if (nride > 0) {
-        const size_t npad = (size_t)round_up(M->n + 1, kPadRows);
-        if (w2) {                                        // the column in the kernel's scaled space: sqrt(w2) .* M[:, j]  (scratch slots 2, 3 of d_nvec)
-            const bool own = ctx->d_nvec && w2 == ctx->d_nvec;
-            LF_TRY(ensure_nvec(ctx, 4 * npad));
-            if (own) w2 = ctx->d_nvec;
+        const GramNvec nv = gram_nvec(M->n, true);
+        if (w2) {                                        // the column in the kernel's scaled space: sqrt(w2) .* M[:, j]  (the two column slots of d_nvec)
+            const bool own = ctx->d_nvec && w2 == ctx->d_nvec + nv.wts;
+            LF_TRY(ensure_nvec(ctx, nv.size));
+            if (own) w2 = ctx->d_nvec + nv.wts;
         }
         for (int b = 0; b < nride; ++b) {
             const double* colp = M->p + (int64_t)(ncols + b) * M->ld;
             if (!w2) { exs[nxu + b] = colp; continue; }
-            double* dst = ctx->d_nvec + (2 + nxu + b) * npad;
-            if (dst == exs[0] || dst == exs[1]) dst = ctx->d_nvec + (2 + ((nxu + b + 1) & 1)) * npad;      // (a view's own column may already sit in a slot)
+            double* dst = ctx->d_nvec + nv.col[nxu + b];
+            if (dst == exs[0] || dst == exs[1]) dst = ctx->d_nvec + nv.col[(nxu + b + 1) & 1];      // (a view's own column may already sit in a slot)
             LF_TRY((run_vec<SignScaleF, 0, NoPost>(ctx, M->n, SignScaleF{colp, nullptr, w2, dst}, 0u, nullptr, NoPost())));
             exs[nxu + b] = dst;
         }
@@ -794,11 +810,11 @@ static int gram_impl(lfpsqp_ctx* ctx, const lfpsqp_mat* M, int ncols_all, const 
     const double* ex1 = exs[1];
     if (w2) {
         // the kernel scales BOTH operands by sqrt(w2): staged in the second half of the n-vector scratch (the first may hold the weights themselves)
-        const size_t npad = (size_t)round_up(M->n + 1, kPadRows);
-        const bool own = ctx->d_nvec && w2 == ctx->d_nvec;              // (a view's combined weights live in the first half already)
-        LF_TRY(ensure_nvec(ctx, 2 * npad));
-        if (own) w2 = ctx->d_nvec;
-        double* sw = ctx->d_nvec + npad;
+        const GramNvec nv = gram_nvec(M->n, false);
+        const bool own = ctx->d_nvec && w2 == ctx->d_nvec + nv.wts;     // (a view's combined weights live in the first half already)
+        LF_TRY(ensure_nvec(ctx, nv.size));
+        if (own) w2 = ctx->d_nvec + nv.wts;
+        double* sw = ctx->d_nvec + nv.sqrtw;
         LF_TRY((run_vec<SqrtWeightF, 0, NoPost>(ctx, M->n, SqrtWeightF{w2, sw}, 0u, nullptr, NoPost())));
         LF_TRY(ensure_part(ctx, (size_t)std::max(gd, go) * pld));         // (run_vec may not shrink it, but keep the reservation next to its use)
         if (shift_sgn) {
@@ -964,11 +980,17 @@ static int rmul_impl(lfpsqp_ctx* ctx, const lfpsqp_mat* In, int kcols, const dou
         hipLaunchKernelGGL(view_rows_kernel, dim3((unsigned)((In->n + 2 * kThreads - 1) / (2 * kThreads)), (unsigned)((rcols + 15) / 16)), dim3(kThreads), 0,
                            ctx->stream, Out->p, Out->ld, In->n, rcols, In->rs, In->ru, dc);
         LF_LAUNCH_CHECK(ctx);
-        if (dc) LF_HIP(ctx, hipStreamSynchronize(ctx->stream));      // (h_m is the context's shared pinned staging block)
+        if (dc) LF_TRY(drain_h_m(ctx));
         return 0;
     }
-    LF_TRY(ensure_small(ctx, (size_t)kcols * rcols + 32 + ((size_t)kcols + kKStep) * ((size_t)rcols + kPanel)));
-    LF_HIP(ctx, hipMemcpyAsync(ctx->small, W_host, sizeof(double) * (size_t)kcols * rcols, hipMemcpyHostToDevice, ctx->stream));
+    double *dW, *wdev;
+    Layout L;                                         // small
+    L.add(dW, (size_t)kcols * rcols);
+    L.add(wdev, ((size_t)kcols + kKStep) * ((size_t)rcols + kPanel), 16);       // W as rmul_kernel stages it: kpad x rpad at most (below)
+    L.skip(32);                                       // tail: purpose unknown; kept
+    LF_TRY(ensure_small(ctx, L.size()));
+    L.carve(ctx->small);
+    LF_HIP(ctx, hipMemcpyAsync(dW, W_host, sizeof(double) * (size_t)kcols * rcols, hipMemcpyHostToDevice, ctx->stream));
     LF_HIP(ctx, hipStreamSynchronize(ctx->stream));   // W_host is caller-owned pageable memory
     const int64_t ntiles = (In->n + kPanel - 1) / kPanel;
     const int64_t cus = ctx->num_cu > 0 ? ctx->num_cu : 1;
@@ -979,17 +1001,16 @@ static int rmul_impl(lfpsqp_ctx* ctx, const lfpsqp_mat* In, int kcols, const dou
     constexpr int kRW = LFPSQP_RMUL_WAVES;    // waves of the W-resident kernel: 8 = two per SIMD, each covers the other's tile epilogue
     if (kcols <= kPanel && rcols <= kPanel && ctx->tune_onepass >= 0) {      // W resident in LDS, persistent grid
         hipLaunchKernelGGL((rmul_resident_kernel<32, 8, 16, kRW>), pgrid, dim3(64 * kRW), 0, ctx->stream, In->p, In->ld, In->n, kcols,
-                           ctx->small, kcols, rcols, Out->p, Out->ld, ntiles);
+                           dW, kcols, rcols, Out->p, Out->ld, ntiles);
     } else if (kcols <= 132 && rcols <= 144 && ctx->tune_onepass >= 0) {     // ... a few columns more (m = 128 + slack / ball)
         hipLaunchKernelGGL((rmul_resident_kernel<33, 9, 11, kRW>), pgrid, dim3(64 * kRW), 0, ctx->stream, In->p, In->ld, In->n, kcols,
-                           ctx->small, kcols, rcols, Out->p, Out->ld, ntiles);
+                           dW, kcols, rcols, Out->p, Out->ld, ntiles);
     } else {
         // W laid out for staging (rmul_kernel): row-major, k padded to the 16-deep step, columns to the 128-wide panel
         const int ncp = (rcols + kPanel - 1) / kPanel, rpad = ncp * kPanel, kpad = (kcols + kKStep - 1) / kKStep * kKStep;
         std::vector<double> Wd((size_t)kpad * rpad, 0.0);
         for (int c = 0; c < rcols; ++c)
             for (int k = 0; k < kcols; ++k) Wd[(size_t)k * rpad + c] = W_host[(size_t)c * kcols + k];
-        double* wdev = ctx->small + (((size_t)kcols * rcols + 15) & ~(size_t)15);
         LF_HIP(ctx, hipMemcpyAsync(wdev, Wd.data(), sizeof(double) * Wd.size(), hipMemcpyHostToDevice, ctx->stream));
         LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
         const int64_t tgroups = (ntiles + 7) / 8;

@@ -153,10 +153,31 @@ struct lfpsqp_ctx {
 namespace lfpsqp {
 
 int set_err(lfpsqp_ctx* ctx, int code, const char* fmt, ...);
-int ensure_part(lfpsqp_ctx* ctx, size_t doubles);
-int ensure_small(lfpsqp_ctx* ctx, size_t doubles);
-int ensure_mvec(lfpsqp_ctx* ctx, size_t doubles);   // d_m / h_m, each `doubles` long
-int ensure_nvec(lfpsqp_ctx* ctx, size_t doubles);   // d_nvec (padded to whole tiles)
+// the grow-only scratch buffers of the context; growing one synchronises the stream and moves the buffer
+int ensure_part(lfpsqp_ctx* ctx, size_t doubles);   // part: a quarter plus 4096 more than asked
+int ensure_small(lfpsqp_ctx* ctx, size_t doubles);  // small: exact
+int ensure_tri(lfpsqp_ctx* ctx, size_t doubles);    // d_tri: exact
+int ensure_mvec(lfpsqp_ctx* ctx, size_t doubles);   // d_m / h_m, each `doubles` + 64 long, whole tiles, d_m zero-filled; voids ctx->pcg_resume
+int ensure_nvec(lfpsqp_ctx* ctx, size_t doubles);   // d_nvec (padded to whole tiles, zero-filled)
+
+// The layout of one of these buffers, declared once: add(p, len) names the regions in order, size() is what to reserve, and carve(base) points
+// every p at its region -- AFTER the ensure_* call (a buffer that grows moves).  A region starts on a multiple of `align` doubles (even by
+// default: the double2 accesses of the kernels); an optional region is add()ed under its condition.  skip(len): a region without a pointer of
+// its own -- a tail kept from before, or one used through its offset (returned; in doubles) in both d_m and h_m.
+struct Layout {
+    struct Region { double** p; size_t at; };
+    Region r[12];
+    int k = 0;
+    size_t n = 0;
+    size_t skip(size_t len, size_t align = 2) {
+        const size_t at = (n + align - 1) / align * align;
+        n = at + len;
+        return at;
+    }
+    void add(double*& p, size_t len, size_t align = 2) { r[k++] = Region{&p, skip(len, align)}; }
+    size_t size() const { return n; }
+    void carve(double* base) const { for (int i = 0; i < k; ++i) *r[i].p = base + r[i].at; }
+};
 int ensure_view(lfpsqp_ctx* ctx);                   // d_view (kViewScratch doubles)
 constexpr int kViewTau = 8;                          // doubles reserved for tau at the head of d_view
 constexpr int kViewScratch = kViewTau + 4 * 1024 + 64;
@@ -191,6 +212,12 @@ inline int64_t ntiles_of(int64_t n, int ks) { return (n + (int64_t)kSlabRows * k
     } while (0)
 
 #define LF_LAUNCH_CHECK(ctx) LF_HIP(ctx, hipGetLastError())
+
+// h_m is the ONE pinned staging block of the context: a call that queued a copy out of it waits here before it returns, or the next call rewrites it
+inline int drain_h_m(lfpsqp_ctx* ctx) {
+    LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
 
 // ---- generic launchers (templates, so they live in the header) -------------
 

@@ -574,13 +574,13 @@ static int pcg_pre_impl(lfpsqp_ctx* ctx, double mu, const lfpsqp_basis* Jop, con
     for (int k = 0; k < kPRing; ++k) hstat[kPRingOff + k] = PST_RUNNING;
     const size_t mm = (size_t)m * m;
     LF_TRY(ensure_small(ctx, mm + 8));
-    LF_TRY(ensure_mvec(ctx, (size_t)6 * m + 64));
-    double* dK = ctx->small;
-    double* out1 = ctx->d_m;                                   // m + 1
-    double* out2 = out1 + round_up(2 * m + 1, 2) + 2;          // m + 1
-    double* tp = out2 + round_up(m + 1, 2) + 2;
-    double* sP = tp + round_up(m, 2);
-    double* c1 = sP + round_up(m, 2);
+    double *dK = ctx->small, *out1, *out2, *tp, *sP, *c1;
+    Layout L;                                                  // d_m
+    L.add(out1, 2 * m + 3);                                    // m + 1 sums in a stride of round_up(2 m + 1, 2) + 2, as it always was
+    L.add(out2, m + 3);                                        // m + 1 sums in round_up(m + 1, 2) + 2
+    L.add(tp, m); L.add(sP, m); L.add(c1, m); L.skip(64);      // (tail: purpose unknown; kept)
+    LF_TRY(ensure_mvec(ctx, L.size()));
+    L.carve(ctx->d_m);
     LF_HIP(ctx, hipMemcpyAsync(dK, P->K, sizeof(double) * mm, hipMemcpyHostToDevice, ctx->stream));
     LF_HIP(ctx, hipMemsetAsync(tp, 0, sizeof(double) * m, ctx->stream));
     LF_HIP(ctx, hipStreamSynchronize(ctx->stream));            // P->K is caller-owned pageable memory
@@ -679,8 +679,10 @@ extern "C" int lfpsqp_pcg(lfpsqp_ctx* ctx, double mu, const lfpsqp_basis* Jop, l
     const bool fused = !sparse && m > 0 && onepass_cw(ctx, m, Z->ld, N) != 0;
     double* US = nullptr;                            // [u = J z (m) ; s = J r (m) ; p'z]
     if (fused) {
-        LF_TRY(ensure_mvec(ctx, (size_t)2 * m + 16));
-        US = ctx->d_m;
+        Layout L;
+        L.add(US, 2 * m + 1); L.skip(14);            // (tail: purpose unknown; kept)
+        LF_TRY(ensure_mvec(ctx, L.size()));
+        L.carve(ctx->d_m);
     }
     int64_t it = 0;
     bool done = maxiter <= 0;

@@ -1429,16 +1429,6 @@ __global__ __launch_bounds__(256) void diags_stack_weights_kernel(DiagsD<C> A, i
         for (int k = 0; k < A.K; ++k) aoff[k * npad + i] = (i + A.s[k] < A.n) ? sx[i] * A.col(k)[i] * sx[i + A.s[k]] : 0.0;
     }
 }
-static int ensure_tri(lfpsqp_ctx* ctx, size_t doubles) {
-    if (doubles <= ctx->tri_cap) return 0;
-    LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_tri) LF_HIP(ctx, hipFree(ctx->d_tri));
-    ctx->d_tri = nullptr;
-    ctx->tri_cap = 0;
-    LF_HIP(ctx, hipMalloc((void**)&ctx->d_tri, doubles * sizeof(double)));
-    ctx->tri_cap = doubles;
-    return 0;
-}
 // the set-up vectors of the reduced operator in ctx->d_tri: K columns of |off| and of sign(off), the two parts of the diagonal weights, a flag;
 // stacked: the diagonal and the K coupling columns of At behind them
 struct TriWeights {
@@ -1446,16 +1436,17 @@ struct TriWeights {
     double *wabs, *sgn, *cpos, *cneg, *anyneg, *adg, *aoff;
     unsigned nblk;
 };
+// ux (N doubles) of the stacked gather path of a coupled solve: the head of d_tri, whose set-up weights are dead once M = U'A U is on the device
+static double* tri_ux(lfpsqp_ctx* ctx) { return ctx->d_tri; }
 static int tri_weights_alloc(lfpsqp_ctx* ctx, int64_t n, int K, bool stacked, TriWeights& w) {
     w.npad = round_up((n > 0 ? n : 1) + 1, kPadRows);
-    LF_TRY(ensure_tri(ctx, (2 * K + 2 + (stacked ? 1 + K : 0)) * (size_t)w.npad + 8));
-    w.wabs = ctx->d_tri;
-    w.sgn = w.wabs + K * w.npad;
-    w.cpos = w.sgn + K * w.npad;
-    w.cneg = w.cpos + w.npad;
-    w.anyneg = w.cneg + w.npad;
-    w.adg = w.anyneg + 8;
-    w.aoff = w.adg + w.npad;
+    const size_t np = (size_t)w.npad;
+    Layout L;
+    L.add(w.wabs, K * np); L.add(w.sgn, K * np); L.add(w.cpos, np); L.add(w.cneg, np); L.add(w.anyneg, 8);
+    w.adg = w.aoff = nullptr;
+    if (stacked) { L.add(w.adg, np); L.add(w.aoff, K * np); }
+    LF_TRY(ensure_tri(ctx, L.size()));
+    L.carve(ctx->d_tri);
     w.nblk = (unsigned)std::min<int64_t>((w.npad + 255) / 256, 4096);
     return 0;
 }
@@ -1577,8 +1568,11 @@ __global__ __launch_bounds__(256) void sphess_edge_weights_kernel(const int32_t*
 static int reduced_operator_sparse(lfpsqp_ctx* ctx, const lfpsqp_mat* Z, int mc, double a0, const double* dg, const lfpsqp_sphess& S, const double* W,
                                    int m, std::vector<double>& Mh, const StackD* sk = nullptr) {
     const int64_t n = S.n, npad = S.npad;
-    LF_TRY(ensure_tri(ctx, 4 * (size_t)npad + 8));
-    double *wabs = ctx->d_tri, *sgn = wabs + npad, *cpos = sgn + npad, *cneg = cpos + npad, *anyneg = cneg + npad;
+    double *wabs, *sgn, *cpos, *cneg, *anyneg;
+    Layout L;
+    L.add(wabs, npad); L.add(sgn, npad); L.add(cpos, npad); L.add(cneg, npad); L.add(anyneg, 8);
+    LF_TRY(ensure_tri(ctx, L.size()));
+    L.carve(ctx->d_tri);
     const unsigned nblk = (unsigned)std::min<int64_t>((npad + 255) / 256, 4096);
     const double *sx = sk ? sk->sx : nullptr, *sy = sk ? sk->sy : nullptr;
     LF_HIP(ctx, hipMemsetAsync(anyneg, 0, sizeof(double), ctx->stream));
@@ -1758,13 +1752,7 @@ static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const
         SA = U->SA;
         wm = (int)U->A->m;
         // (the scratch n-vector is read by whole tiles, like every n-vector of the library: padded to kPadRows, SpPlainV::load)
-        LF_TRY(ensure_small(ctx, (size_t)wm * m + 2 * (size_t)wm + 64 + (stacked ? (size_t)round_up(N, kPadRows) + 2 : 0)));
-        dWs = ctx->small;
-        tA = dWs + (((size_t)wm * m + 1) & ~(size_t)1);
-        uA = tA + ((wm + 1) & ~1);
-        if (stacked) tmpN = uA + ((wm + 1) & ~1);
-        LF_HIP(ctx, hipMemcpyAsync(dWs, U->W, sizeof(double) * (size_t)wm * m, hipMemcpyHostToDevice, ctx->stream));
-        LF_HIP(ctx, hipStreamSynchronize(ctx->stream));                 // U->W is caller-owned pageable memory
+        LF_TRY(factored_setup(ctx, U->A, U->W, m, &dWs, &tA, &uA, stacked ? (size_t)round_up(N, kPadRows) + 2 : 0, &tmpN));
     }
     if (SF && !SA) return set_err(ctx, LFPSQP_ERR_UNSUPPORTED, "basis in factored form on the nonzeros (Z == NULL, SA given): shape not covered; materialise Z");
     const int nxs = SA ? wm - (int)SA->m : 0;
@@ -1818,29 +1806,26 @@ static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const
     double* dTriM = nullptr;
     double *lrUtV = nullptr, *lrSig = nullptr, *lrVdraw = nullptr, *lrVdc = nullptr, *lrVtv = nullptr;
     if (fused) {
-        LF_TRY(ensure_mvec(ctx, (size_t)3 * m + (DF ? 3 * (size_t)mc + 16 : 0) + 2 * kLRMax + 24 + (kLR > 0 ? (size_t)m * kLRMax + 4 * kLRMax + 8 : 0)));
-        T12 = ctx->d_m;                                  // [t1 (m); t2 (m); rp'gp; gp'gp; g'Ag; g'Ad; d'Ad (; V'gp)]
-        t3 = ctx->d_m + round_up(2 * m + ns, 2);
-        double* tail = t3 + round_up(m, 2);
+        Layout L;                                        // d_m
+        L.add(T12, 2 * m + ns);                          // [t1 (m); t2 (m); rp'gp; gp'gp; g'Ag; g'Ad; d'Ad (; V'gp)]
+        L.add(t3, m);
         if (DF) {
-            Traw = tail;                                 // the kernel's raw sums over the generator's columns
-            uDF = Traw + round_up(2 * mc + ns, 2);       // W Utr: the coefficients of the first product
-            tail = uDF + round_up(mc, 2);
+            L.add(Traw, 2 * mc + ns);                    // the kernel's raw sums over the generator's columns
+            L.add(uDF, mc);                              // W Utr: the coefficients of the first product
         }
-        if (kLR > 0) {
-            lrUtV = tail; lrSig = lrUtV + (size_t)m * kLRMax; lrVdraw = lrSig + kLRMax; lrVdc = lrVdraw + kLRMax; lrVtv = lrVdc + kLRMax;
-        }
+        if (kLR > 0) { L.add(lrUtV, (size_t)m * kLRMax); L.add(lrSig, kLRMax); L.add(lrVdraw, kLRMax); L.add(lrVdc, kLRMax); L.add(lrVtv, kLRMax); }
+        L.skip(2 * kLRMax + 24 + (DF ? 16 : 0) + (kLR > 0 ? 8 : 0));      // tail: the slack of the earlier size formula (purpose unknown; kept whole)
+        LF_TRY(ensure_mvec(ctx, L.size()));
+        L.carve(ctx->d_m);
         if (DF || cop) {
-            const size_t wsz = DF ? (size_t)round_up((int64_t)mc * m, 2) : 0;
-            LF_TRY(ensure_small(ctx, wsz + (cop ? (size_t)m * m : 0) + 64));
-            if (DF) {
-                dWf = ctx->small;
-                LF_HIP(ctx, hipMemcpyAsync(dWf, U->W, sizeof(double) * (size_t)mc * m, hipMemcpyHostToDevice, ctx->stream));
-            }
-            if (cop) {
-                dTriM = ctx->small + wsz;
-                LF_HIP(ctx, hipMemcpyAsync(dTriM, triMh.data(), sizeof(double) * (size_t)m * m, hipMemcpyHostToDevice, ctx->stream));
-            }
+            Layout Ls;                                   // small
+            if (DF) Ls.add(dWf, (size_t)mc * m);
+            if (cop) Ls.add(dTriM, (size_t)m * m);
+            Ls.skip(64);                                 // tail: purpose unknown; kept
+            LF_TRY(ensure_small(ctx, Ls.size()));
+            Ls.carve(ctx->small);
+            if (DF) LF_HIP(ctx, hipMemcpyAsync(dWf, U->W, sizeof(double) * (size_t)mc * m, hipMemcpyHostToDevice, ctx->stream));
+            if (cop) LF_HIP(ctx, hipMemcpyAsync(dTriM, triMh.data(), sizeof(double) * (size_t)m * m, hipMemcpyHostToDevice, ctx->stream));
             LF_HIP(ctx, hipStreamSynchronize(ctx->stream));             // U->W is caller-owned pageable memory (and triMh a local)
         }
     }
@@ -1933,12 +1918,11 @@ static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const
                 if constexpr (ST) return run_vec<TriPrepSF<B, INIT>, 0, NoPost>(ctx, N, TriPrepSF<B, INIT>{Ab, hs, sk.Dx, sk.Dy, src, dsrc, ad, q, scal, istat}, 0u, nullptr, NoPost());
                 else return run_vec<TriPrepF<B, INIT>, 0, NoPost>(ctx, N, TriPrepF<B, INIT>{Ab, src, dsrc, ad, q, scal, istat}, 0u, nullptr, NoPost());
             });
-        // run-time distances or index slots: A d stored first, then the gather of the neighbours' rr (stacked: of ux, kept in the set-up's scratch,
-        // which is free once M is on the device)
+        // run-time distances or index slots: A d stored first, then the gather of the neighbours' rr (stacked: of ux)
         return with_gathers(*cop, N, N, [&](auto Ab) -> int {
             using D = decltype(Ab);
             if constexpr (ST) {
-                double* ux = ctx->d_tri;
+                double* ux = tri_ux(ctx);
                 LF_TRY((run_vec<DiagsPrepSF<D, INIT>, 0, NoPost>(ctx, N, DiagsPrepSF<D, INIT>{Ab, hs, sk.Dx, sk.Dy, src, dsrc, ad, ux, scal, istat}, 0u, nullptr, NoPost())));
                 return run_vec<DiagsGatherF<D>, 0, NoPost>(ctx, N, DiagsGatherF<D>{Ab, ux, nullptr, q, scal, istat}, 0u, nullptr, NoPost());
             } else {
@@ -2122,10 +2106,12 @@ static int projcg_impl(lfpsqp_ctx* ctx, lfpsqp_vec* x, lfpsqp_vec* lambda, const
 int lfpsqp::placement_probe(lfpsqp_ctx* ctx, const lfpsqp_mat* M, int ncols, double* g, double* d, double* a, int reps, double* ms) {
     *ms = -1.0;
     if (!M || M->n <= 0 || ncols < 4 || ncols > M->m || onepass_cw(ctx, ncols, M->ld, M->n) == 0) return 0;
-    LF_TRY(ensure_mvec(ctx, (size_t)3 * ncols + 24));               // (also invalidates any resumable projcg state: scal is rewritten below)
-    double* T12 = ctx->d_m;
-    double* Utr = ctx->d_m + round_up(2 * ncols + 5, 2);           // zeros: the first product vanishes
-    LF_HIP(ctx, hipMemsetAsync(ctx->d_m, 0, sizeof(double) * ((size_t)3 * ncols + 24), ctx->stream));
+    double *T12, *Utr;                                              // (Utr zeros: the first product vanishes)
+    Layout L;
+    L.add(T12, 2 * ncols + 5); L.add(Utr, ncols); L.skip(18);       // (tail: purpose unknown; kept)
+    LF_TRY(ensure_mvec(ctx, L.size()));                             // (also invalidates any resumable projcg state: scal is rewritten below)
+    L.carve(ctx->d_m);
+    LF_HIP(ctx, hipMemsetAsync(ctx->d_m, 0, sizeof(double) * L.size(), ctx->stream));
     hipLaunchKernelGGL((post_kernel<InitState>), dim3(1), dim3(1), 0, ctx->stream, ctx->scal, InitState{ctx->scal, ctx->istat, 0.0, (int64_t)1 << 40});
     LF_LAUNCH_CHECK(ctx);
     const StackD sk{0, nullptr, nullptr, nullptr, nullptr};

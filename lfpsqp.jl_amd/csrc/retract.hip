@@ -705,6 +705,17 @@ static int cons_raw(lfpsqp_ctx* ctx, const lfpsqp_constraints* cons, const doubl
     return 0;
 }
 
+// d_m / h_m as cons_eval and the host loops that call it share them: cons_eval's raw products (m_lin + 1 of at most m constraints, reserved as
+// m + 8) in front, the caller's own m-vector behind them
+struct ConsStage { size_t own, size; };
+static ConsStage cons_stage(int m, size_t tail) {
+    Layout L;
+    L.skip(m + 8);
+    const size_t own = L.skip(m);
+    L.skip(tail);
+    return ConsStage{own, L.size()};
+}
+
 int cons_eval(lfpsqp_ctx* ctx, const lfpsqp_constraints* cons, const lfpsqp_vec* x, double* cval) {
     const int ml = (int)cons->m_lin;
     const int mt = ml + (cons->has_ball ? 1 : 0);
@@ -928,8 +939,7 @@ int lfpsqp_constraints_hess_diag(lfpsqp_ctx* ctx, const lfpsqp_constraints* cons
     LF_TRY(ensure_mvec(ctx, (size_t)ml + 8));
     for (int j = 0; j < ml; ++j) ctx->h_m[j] = lam[j];
     LF_HIP(ctx, hipMemcpyAsync(ctx->d_m, ctx->h_m, sizeof(double) * ml, hipMemcpyHostToDevice, ctx->stream));
-    LF_HIP(ctx, hipStreamSynchronize(ctx->stream));            // h_m is the context's SHARED pinned staging block: the copy must have read it
-                                                               // before this call returns and another call writes it (as stage_qw does)
+    LF_TRY(drain_h_m(ctx));
     if (ew->Asp) return run_vec<EwHessVecF, 0, NoPost>(ctx, N, EwHessVecF{he, ell_rows(ew->Asp, ctx->d_m)}, 0u, nullptr, NoPost());
     return run_gemv_n<EwHessE, 0, NoPost>(ctx, ew->A, ml, N, ctx->d_m, he, nullptr, NoPost());
 }
@@ -945,7 +955,8 @@ int lfpsqp_retract_nr(lfpsqp_ctx* ctx, const lfpsqp_basis* U, const double* Sigm
     const int m = (int)m64;
     const bool ineq = idata != nullptr;
     LF_ARG(ctx, ineq == (U->Dx != nullptr));
-    LF_TRY(ensure_mvec(ctx, (size_t)2 * m + 8));
+    const ConsStage stage = cons_stage(m, 0);       // (the device loop brings c(x) back through the head of h_m)
+    LF_TRY(ensure_mvec(ctx, stage.size));
 
     if (!cfun && m <= kNRMaxM) {
         // ---- device-resident loop: no host round trip per iteration ------------------------------------------
@@ -963,17 +974,17 @@ int lfpsqp_retract_nr(lfpsqp_ctx* ctx, const lfpsqp_basis* U, const double* Sigm
         // without a one-pass kernel): it then streams Jct with W*ddelta instead of Z with ddelta, so a basis in factored form (U->Z == NULL) works
         const int cw = (Ssp || wm) ? 1 : cwd;
         LF_ARG(ctx, U->Z || wm);
-        const size_t wsz = cw ? (((size_t)wm * m + (size_t)wm + 3) & ~(size_t)1) : 0;     // W, W*delta and one scalar (qw . W*delta) behind it
-        LF_TRY(ensure_small(ctx, 2 * mm + wsz + 8 * (size_t)m + 256));
-        double* dD = ctx->small;
-        double* dVt = dD + mm;
-        double* dW = dVt + mm;
-        double* dwdelta = dW + (size_t)(cw ? wm : 0) * m;
-        double* dSig = dW + wsz;
-        double* db = dSig + m;
-        double* dcval = db + m;
-        double* ddelta = dcval + m;
-        double* draw = ddelta + m + (m & 1);          // keep the reduce output 16-byte aligned
+        double *dD, *dVt, *dW, *dwdelta, *dSig, *db, *dcval, *ddelta, *draw;
+        Layout L;                                     // small; regions packed (align 1) where they always were
+        L.add(dD, mm, 1); L.add(dVt, mm, 1);
+        L.add(dW, cw ? (size_t)wm * m : 0, 1);
+        L.add(dwdelta, cw ? (size_t)wm + 2 : 0, 1);   // W*delta, one scalar (qw . W*delta) behind it, one spare
+        L.add(dSig, m); L.add(db, m, 1); L.add(dcval, m, 1); L.add(ddelta, m + (m & 1), 1);
+        // the raw c! products (ml + 1 <= m + 1) as the reduction writes them; the earlier formula left 4 m + 256 doubles from here on without saying
+        // how far the kernels reach: kept, as this region's length and a tail
+        L.add(draw, (size_t)4 * m, 1); L.skip(256, 1);
+        LF_TRY(ensure_small(ctx, L.size()));
+        L.carve(ctx->small);
         if (cw) LF_HIP(ctx, hipMemcpyAsync(dW, U->W, sizeof(double) * (size_t)wm * m, hipMemcpyHostToDevice, ctx->stream));
         LF_HIP(ctx, hipMemcpyAsync(dVt, Vt, sizeof(double) * mm, hipMemcpyHostToDevice, ctx->stream));
         LF_HIP(ctx, hipMemcpyAsync(dSig, Sigma, sizeof(double) * m, hipMemcpyHostToDevice, ctx->stream));
@@ -1064,12 +1075,11 @@ int lfpsqp_retract_nr(lfpsqp_ctx* ctx, const lfpsqp_basis* U, const double* Sigm
     std::vector<double> D((size_t)m * m), tmp(m), tmp2(m), dc(m);
     for (int j = 0; j < m; ++j)                                       // :126-130  D[k,j] = Vt[k,j] / Sigma[k]
         for (int k = 0; k < m; ++k) D[(size_t)j * m + k] = Vt[(size_t)j * m + k] / Sigma[k];
-    // staging vector for delta on the device (offset past the slots cons_eval uses)
-    lfpsqp_vec tv;
-    tv.p = ctx->d_m + round_up(m + 8, 2);
+    lfpsqp_vec tv;                                                    // delta staged on the device
+    tv.p = ctx->d_m + stage.own;
     tv.n = m;
     tv.cap = m;
-    double* h_delta = ctx->h_m + round_up(m + 8, 2);
+    double* h_delta = ctx->h_m + stage.own;
 
     int64_t i = 0;
     while (i < maxiter) {
@@ -1185,16 +1195,19 @@ int lfpsqp_retract_nr_batch(lfpsqp_ctx* ctx, const lfpsqp_basis* U, const double
     const size_t mm = (size_t)m * m;
     const int wstride = (int)round_up(wm, 2);
     const int rawn = NBk * ml + NBk;
-    LF_TRY(ensure_small(ctx, (size_t)NBk * mm + mm + (size_t)wm * m + (size_t)NBk * wstride + 8 * (size_t)m * (NBk + 1) + rawn + 256));
-    double* dD = ctx->small;                           // NBk x (m x m)
-    double* dVt = dD + (size_t)NBk * mm;
-    double* dW = dVt + mm;
-    double* dwdelta = dW + (size_t)wm * m + ((wm * m) & 1);
-    double* dSig = dwdelta + (size_t)NBk * wstride;
-    double* db = dSig + m + (m & 1);
-    double* dcval = db + m + (m & 1);                  // NBk x m
-    double* ddelta = dcval + (size_t)NBk * m + ((NBk * m) & 1);
-    double* draw = ddelta + (size_t)NBk * m + ((NBk * m) & 1);   // [NBk x ml products ; NBk ball partials]
+    double *dD, *dVt, *dW, *dwdelta, *dSig, *db, *dcval, *ddelta, *draw;
+    Layout L;                                          // small; each region an even number of doubles behind the one before (align 1: m x m may be odd)
+    L.add(dD, (size_t)NBk * mm, 1);                    // NBk x (m x m)
+    L.add(dVt, mm, 1);
+    L.add(dW, (size_t)round_up((int64_t)wm * m, 2), 1);
+    L.add(dwdelta, (size_t)NBk * wstride, 1);
+    L.add(dSig, (size_t)round_up(m, 2), 1); L.add(db, (size_t)round_up(m, 2), 1);
+    L.add(dcval, (size_t)round_up((int64_t)NBk * m, 2), 1);      // NBk x m
+    L.add(ddelta, (size_t)round_up((int64_t)NBk * m, 2), 1);
+    L.add(draw, rawn, 1);                              // [NBk x ml products ; NBk ball partials]
+    L.skip((size_t)6 * m * (NBk + 1) + 256, 1);        // tail: what the earlier 8 m (NBk + 1) + 256 left beside the regions above; purpose unknown, kept
+    LF_TRY(ensure_small(ctx, L.size()));
+    L.carve(ctx->small);
     LF_HIP(ctx, hipMemcpyAsync(dVt, Vt, sizeof(double) * mm, hipMemcpyHostToDevice, ctx->stream));
     LF_HIP(ctx, hipMemcpyAsync(dW, U->W, sizeof(double) * (size_t)wm * m, hipMemcpyHostToDevice, ctx->stream));
     LF_HIP(ctx, hipMemcpyAsync(dSig, Sigma, sizeof(double) * m, hipMemcpyHostToDevice, ctx->stream));
@@ -1303,18 +1316,19 @@ int lfpsqp_retract_pp(lfpsqp_ctx* ctx, const lfpsqp_constraints* cons, lfpsqp_cf
     const int m = (int)m64;
     const int64_t N = Jct->n;
     if (ineq) LF_ARG(ctx, Dx && Dy && S && w->tmp_w && w->h && w->DxS && w->DyS && w->ones && w->zeros && idata->n == N);
+    const ConsStage stage = cons_stage(m, (size_t)6 * m + 120);      // (tail: what the earlier 8 m + 128 left beside the two regions; purpose unknown, kept)
     {
         // everything this call will ask of the m-vector staging area, reserved NOW: the pointers taken from it below must survive the Gram
         // passes and the preconditioned solves of the loop (ensure_mvec reallocates when it has to grow)
         const size_t np = ((size_t)m + 127) / 128;
         const size_t gram_doubles = w->precondition ? np * (np + 1) / 2 * 16384 + 64 : 0;
-        LF_TRY(ensure_mvec(ctx, std::max((size_t)8 * m + 128, gram_doubles)));
+        LF_TRY(ensure_mvec(ctx, std::max(stage.size, gram_doubles)));
     }
     lfpsqp_vec cdev;                       // replicated device copy of cval (rhs of J' c)
-    cdev.p = ctx->d_m + round_up(m + 8, 2);
+    cdev.p = ctx->d_m + stage.own;
     cdev.n = m;
     cdev.cap = m;
-    double* h_c = ctx->h_m + round_up(m + 8, 2);
+    double* h_c = ctx->h_m + stage.own;
     // fulljac in lfpsqp_basis form (src/retractions.jl:324): plain Jct, or [[diag Dx.*S, Jct]; [diag Dy.*S, 0]]
     lfpsqp_basis Jop;
     Jop.Z = Jct;

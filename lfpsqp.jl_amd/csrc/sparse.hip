@@ -246,12 +246,15 @@ struct SpFactoredNF {  // y = alpha * ([S | X] u) + beta * y
         else if (v0) y[i] = o.x;
     }
 };
-int factored_setup(lfpsqp_ctx* ctx, const lfpsqp_mat* A, const double* W_host, int m, double** dW, double** tA, double** uA) {
+int factored_setup(lfpsqp_ctx* ctx, const lfpsqp_mat* A, const double* W_host, int m, double** dW, double** tA, double** uA, size_t extra_len,
+                   double** extra) {
     const int wm = (int)A->m;
-    LF_TRY(ensure_small(ctx, (size_t)wm * m + 2 * (size_t)wm + 64));
-    *dW = ctx->small;
-    *tA = *dW + (((size_t)wm * m + 1) & ~(size_t)1);
-    *uA = *tA + ((wm + 1) & ~1);
+    Layout L;
+    L.add(*dW, (size_t)wm * m); L.add(*tA, wm); L.add(*uA, wm);
+    if (extra_len) L.add(*extra, extra_len);
+    L.skip(64);                                                     // tail: purpose unknown; kept
+    LF_TRY(ensure_small(ctx, L.size()));
+    L.carve(ctx->small);
     LF_HIP(ctx, hipMemcpyAsync(*dW, W_host, sizeof(double) * (size_t)wm * m, hipMemcpyHostToDevice, ctx->stream));
     LF_HIP(ctx, hipStreamSynchronize(ctx->stream));                 // W_host is caller-owned pageable memory
     return 0;
@@ -669,7 +672,9 @@ int sp_gram(lfpsqp_ctx* ctx, const lfpsqp_spmat* S, const lfpsqp_mat* X, int x0,
         LF_TRY(read_back(ctx, ctx->scal + 40, &B, 1));
     }
     if (!(B == B) || B > 1e200 || (B != 0.0 && B < 1e-200)) return LFPSQP_ERR_UNSUPPORTED;      // (B is global: every rank decides alike)
-    LF_TRY(ensure_small(ctx, (size_t)ms * ms + 16));
+    Layout L;                                                 // small: the ms x ms block at its head (used as ctx->small below), a tail of unknown purpose (kept)
+    L.skip((size_t)ms * ms); L.skip(16, 1);
+    LF_TRY(ensure_small(ctx, L.size()));
     LF_HIP(ctx, hipMemsetAsync(ctx->small, 0, sizeof(double) * (size_t)ms * ms, ctx->stream));
     if (ms > 0 && B != 0.0) {
         int E = 0;

@@ -313,7 +313,13 @@ extern "C" int lfpsqp_tangent_step(lfpsqp_ctx* ctx, const lfpsqp_basis* U, const
     }
     // 2. coefficients of the first products onto the device: [u1 | (uB) | lam], each ms long; then the raw sums and the folded ones
     const int ms = (int)round_up(m, 2);
-    LF_TRY(ensure_mvec(ctx, (size_t)7 * ms + 64));
+    double *t, *raw, *folded;
+    Layout L;                                               // d_m (the coefficients t come through the head of h_m)
+    L.add(t, 3 * ms);
+    L.add(raw, 2 * ms + 8);                                 // [second products (1 or 2 x m) ; the functor's sums ; u'v terms]: at most 2 m + 6
+    L.add(folded, 2 * ms + 56);                             // the same with a view's rank-one term folded into the second products: at most 2 m + 4
+    LF_TRY(ensure_mvec(ctx, L.size()));
+    L.carve(ctx->d_m);
     const int nlam = stacked ? m : ((mode == 2) ? (int)cons->m_lin : 0);     // last coefficient vector: lam (bounds: Jct lam; nonlinear class: A lam)
     const int slotB = initf ? 1 : -1, slotL = initf ? 2 : 1;
     for (int k = 0; k < m; ++k) {
@@ -321,14 +327,10 @@ extern "C" int lfpsqp_tangent_step(lfpsqp_ctx* ctx, const lfpsqp_basis* U, const
         if (slotB >= 0) ctx->h_m[slotB * ms + k] = uB[k];
         ctx->h_m[slotL * ms + k] = k < nlam ? lam[k] : 0.0;
     }
-    // (only the slots written above travel: 2 or 3 coefficient vectors; the layout of d_m -- t | raw | folded inside 7 ms + 64 doubles -- is checked below)
+    // (only the slots written above travel: 2 or 3 coefficient vectors)
     LF_HIP(ctx, hipMemcpyAsync(ctx->d_m, ctx->h_m, sizeof(double) * (size_t)(slotL + 1) * ms, hipMemcpyHostToDevice, ctx->stream));
-    LF_HIP(ctx, hipStreamSynchronize(ctx->stream));       // h_m is the context's shared pinned staging block (the next call may rewrite it)
-    double* t = ctx->d_m;
-    double* raw = ctx->d_m + 3 * ms;                        // [second products (1 or 2 x m) ; the functor's sums ; u'v terms]
-    double* folded = raw + 2 * ms + 8;                      // the same with a view's rank-one term folded into the second products
+    LF_TRY(drain_h_m(ctx));
     const int nvp = initf ? 2 : 1, nredf = initf ? 4 : 1;   // second-product vectors; functor sums ahead of the u'v terms
-    LF_ARG(ctx, nvp * m + (initf ? 6 : 2) <= 2 * ms + 8 && nvp * m + nredf <= 2 * ms + 56);        // raw and folded hold what the pass and the fold write
     double *dW, *tA, *uA;
     LF_TRY(factored_setup(ctx, A, U->W, rank, &dW, &tA, &uA));
     double* stash = work->Utr->p + m;                       // INIT_PROJCG: [t1 (m); t2 (m); r0'g0; g0'g0; g0'A g0; 0; 0] for lfpsqp_projcg's START_PROJECTED
