@@ -599,6 +599,46 @@ int lfpsqp_sphess_like(lfpsqp_ctx* ctx, const lfpsqp_sphess* W, lfpsqp_sphess** 
 int lfpsqp_sphess_edge_eval(lfpsqp_ctx* ctx, const lfpsqp_sphess* W, int kind, double delta, double scale, const lfpsqp_vec* x, double* f,
                             lfpsqp_vec* grad, lfpsqp_vec* diag, lfpsqp_sphess* H);
 
+/* SEVERAL UNKNOWNS PER VERTEX: points in the plane or in space coupled by a function of their distance -- spring and truss networks with a rest
+ * length, graph and mesh layout, sensor localisation, vector-valued edge-preserving smoothing.  The unknowns are interleaved, x[dim*p + c] =
+ * component c of point p, and the Hessian of  scale * sum_e w_e psi(x_p - x_q)  is an ordinary handle: per point edge a dense dim x dim block, per
+ * point the entries between its own components -- row width (dim - 1) + dim * deg(p), so at most 15 neighbours per point for dim = 2 and 10 for
+ * dim = 3 within LFPSQP_SPHESS_MAX_ROW.  The solver entries above take such a handle as any other.
+ * lfpsqp_sphess_create_points: dim is 2 or 3 and n >= dim*npoints; rows >= dim*npoints carry no couplings (the slack row of a ball constraint).
+ * (pi, pj, w): nedges undirected edges between POINTS (0-based, any order; duplicates, mirrored ones included, add up as for lfpsqp_sphess_create).
+ * Expanded on the host and handed to lfpsqp_sphess_create: all dim^2 entries between dim*p + c and dim*q + c' with the value w_pq, and for every
+ * point the dim (dim - 1) / 2 entries between its own components with the value 0.0 (the slot stays).  LFPSQP_ERR_ARG: p == q, an index outside
+ * [0, npoints), a non-finite weight, dim outside {2, 3}, n < dim*npoints.  LFPSQP_ERR_UNSUPPORTED: a point with more than 15 (dim 2) or 10 (dim 3)
+ * distinct neighbours -- lfpsqp_last_error names the degree and the limit; dim*npoints >= 2^31.
+ * lfpsqp_sphess_points_info: npoints and dim as created, also for a handle made by lfpsqp_sphess_like of such a handle; 0 and 0 for every other
+ * handle.  Either output may be NULL.
+ * lfpsqp_sphess_pair_eval: the counterpart of lfpsqp_sphess_edge_eval, with its conventions: W (made by lfpsqp_sphess_create_points, or a handle on
+ * its pattern) holds the weights and is never written; H is another handle on W's pattern made by lfpsqp_sphess_like; any of f, grad, diag and H
+ * may be NULL (f alone: a kernel that writes no vector); grad and diag are ADDED to, their entries >= dim*npoints are untouched; x may be longer
+ * than dim*npoints.  Per point edge t = x_p - x_q in R^dim and q = |t|^2, an fma chain over the components in order:
+ *     kind 0: psi = q/2                                      a = 1          b = 0                               (delta ignored)
+ *     kind 1: psi = (r - l)^2 / 2,  r = sqrt(q)              a = 1 - l/r    b = l / (r q)                       (a spring; l = delta, finite and >= 0)
+ *     kind 2: psi = q / (s + 1),  s = sqrt(1 + q/delta^2)    a = 1/s        b = -1 / (delta^2 s (1 + q/delta^2))  (delta finite and > 0)
+ * (kind 2 is the radial pseudo-Huber function delta^2 (s - 1) in its form without cancellation; convex).  grad psi = a t, the Hessian block is
+ * B = a I + b (t t'):
+ *     *f                  = scale * sum_e w_e psi(t)                          (each edge once: the row form's sum, halved -- exact)
+ *     grad_(p,c)         += scale * sum_{q ~ p} w_pq a t_c                    (a row's neighbours in slot order, one fma each, then one fma with scale)
+ *     diag_(p,c)         += scale * sum_{q ~ p} w_pq (a + b t_c^2)
+ *     H at ((p,c),(q,c')) = -(scale w_pq) (a [c == c'] + b (t_c t_c'))        in BOTH forms
+ *     H at ((p,c),(p,c')) = scale * sum_{q ~ p} w_pq b (t_c t_c')             in BOTH forms
+ * The product t_c t_c' is formed before it meets b, so the two triangles of H hold the same bits, and the edge form holds the bits of the row form
+ * (an intra-point entry of the edge form is copied from the row form).  With kind 0 the stored values are exactly -(scale w_pq) on the (c, c)
+ * entries and 0.0 elsewhere.  Kind 1 with coincident endpoints (q == 0, l > 0) is a singularity of the potential: the outputs are then NOT FINITE,
+ * and nothing is checked on the device -- as for the values of lfpsqp_sphess_set_values, a caller that cannot vouch for its points checks on the host.
+ * LFPSQP_ERR_ARG: W not a handle of points; kind outside 0 .. 2; kind 1 with delta not finite or < 0; kind 2 with delta not finite or <= 0; scale
+ * not finite; x, grad or diag shorter than dim*npoints; grad or diag aliasing x or each other; H on another pattern or H == W.
+ * LFPSQP_ERR_UNSUPPORTED: a communicator, as for lfpsqp_sphess_edge_eval. */
+int lfpsqp_sphess_create_points(lfpsqp_ctx* ctx, int64_t n, int64_t npoints, int dim, int64_t nedges, const int64_t* pi, const int64_t* pj,
+                                const double* w, lfpsqp_sphess** out);
+int lfpsqp_sphess_points_info(const lfpsqp_sphess* S, int64_t* npoints, int64_t* dim);
+int lfpsqp_sphess_pair_eval(lfpsqp_ctx* ctx, const lfpsqp_sphess* W, int kind, double delta, double scale, const lfpsqp_vec* x, double* f,
+                            lfpsqp_vec* grad, lfpsqp_vec* diag, lfpsqp_sphess* H);
+
 /* VALUES SUPPLIED BY THE CALLER on a fixed pattern: the structure / values contract of a sparse NLP interface (declare the Hessian's structure
  * once, fill an array of values per iteration) for a Lagrangian Hessian that lfpsqp_sphess_edge_eval cannot express.
  * lfpsqp_sphess_map_create: built ONCE on the host from nnz triplet positions (rows, cols) (0-based, any order) against the pattern of S, and

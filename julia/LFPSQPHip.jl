@@ -259,6 +259,9 @@ c_sphess_info(S, n, nedges, kr, ke) = ccall((:lfpsqp_sphess_info, lib), Cint, (P
 c_sphess_mul(ctx, a0, dg, S, v, out) = ccall((:lfpsqp_sphess_mul, lib), Cint, (Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), ctx, a0, dg, S, v, out)
 c_sphess_like(ctx, W, out) = ccall((:lfpsqp_sphess_like, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}), ctx, W, out)
 c_sphess_edge_eval(ctx, W, kind, delta, scale, x, f, grad, diag, H) = ccall((:lfpsqp_sphess_edge_eval, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Float64, Float64, Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), ctx, W, kind, delta, scale, x, f, grad, diag, H)
+c_sphess_create_points(ctx, n, npoints, dim, nedges, pi, pj, w, out) = ccall((:lfpsqp_sphess_create_points, lib), Cint, (Ptr{Cvoid}, Int64, Int64, Cint, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ref{Ptr{Cvoid}}), ctx, n, npoints, dim, nedges, pi, pj, w, out)
+c_sphess_points_info(S, npoints, dim) = ccall((:lfpsqp_sphess_points_info, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), S, npoints, dim)
+c_sphess_pair_eval(ctx, W, kind, delta, scale, x, f, grad, diag, H) = ccall((:lfpsqp_sphess_pair_eval, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Float64, Float64, Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), ctx, W, kind, delta, scale, x, f, grad, diag, H)
 c_projcg_sparse(ctx, x, lam, a0, dg, S, Av, U, b, c, tol, maxit, nglob, flags, work, iters, nr) = ccall((:lfpsqp_projcg_sparse, lib), Cint,
     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{CBasis}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Int64, Int64, Cint, Ref{CWork}, Ref{Int64}, Ref{Float64}),
     ctx, x, lam, a0, dg, S, Av, U, b, c, tol, maxit, nglob, flags, work, iters, nr)
@@ -686,6 +689,33 @@ end
 function edge_eval!(W::SparseHessian, kind::Integer, delta::Float64, scale::Float64, x::DeviceVector; grad=nothing, diag=nothing, out=nothing, want_f::Bool=true)
     f = Ref{Float64}(0.0)
     check(W.ctx, c_sphess_edge_eval(W.ctx.h, W.h, Cint(kind), delta, scale, x.h, want_f ? f : Ptr{Float64}(C_NULL),
+                                    grad === nothing ? C_NULL : grad.h, diag === nothing ? C_NULL : diag.h, out === nothing ? C_NULL : out.h))
+    return want_f ? f[] : nothing
+end
+# Points of dim = 2 or 3 unknowns each, interleaved (x[dim (p - 1) + c] = component c of point p): the handle of a pair term over the 1-based
+# undirected point edges (I[e], J[e]) with weights V[e] (lfpsqp_sphess_create_points); n >= dim npoints rows, the rows behind the points uncoupled.
+function SparseHessianPoints(ctx::HipContext, n::Integer, npoints::Integer, dim::Integer, I::Vector{Int}, J::Vector{Int}, V::Vector{Float64})
+    length(I) == length(J) == length(V) || error("I, J and V are of different lengths")
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ctx, c_sphess_create_points(ctx.h, Int64(n), Int64(npoints), Cint(dim), Int64(length(V)), Int64.(I .- 1), Int64.(J .- 1), V, r))
+    nn = Ref{Int64}(0); ne = Ref{Int64}(0); kr = Ref{Int64}(0); ke = Ref{Int64}(0)
+    check(ctx, c_sphess_info(r[], nn, ne, kr, ke))
+    S = SparseHessian(ctx, r[], Int(nn[]), Int(ne[]), Int(kr[]), Int(ke[]))
+    finalizer(x -> c_sphess_free(x.ctx.h, x.h), S)
+    return S
+end
+# (npoints, dim) of a handle of points or of a handle made by `like` of one; (0, 0) for every other handle
+function points_info(S::SparseHessian)
+    np = Ref{Int64}(0); d = Ref{Int64}(0)
+    check(S.ctx, c_sphess_points_info(S.h, np, d))
+    return Int(np[]), Int(d[])
+end
+# The pair term scale Σ_e w_e ψ(x_p - x_q) between points (lfpsqp_sphess_pair_eval; kind 0: |t|²/2, 1: a spring of rest length delta, 2: the radial
+# pseudo-Huber function with scale delta), with the conventions of edge_eval!: the value is returned, `grad` and `diag` are added to, `out` (a handle
+# made by `like`) receives the Hessian's entries, W is never modified.
+function pair_eval!(W::SparseHessian, kind::Integer, delta::Float64, scale::Float64, x::DeviceVector; grad=nothing, diag=nothing, out=nothing, want_f::Bool=true)
+    f = Ref{Float64}(0.0)
+    check(W.ctx, c_sphess_pair_eval(W.ctx.h, W.h, Cint(kind), delta, scale, x.h, want_f ? f : Ptr{Float64}(C_NULL),
                                     grad === nothing ? C_NULL : grad.h, diag === nothing ? C_NULL : diag.h, out === nothing ? C_NULL : out.h))
     return want_f ? f[] : nothing
 end
@@ -2216,7 +2246,7 @@ optimize(ctx::HipContext, f, grad!, c!, jac_c!, d!, jac_d!, hess_lag_vec!, x0::V
 
 export HipContext, HipError, DeviceOptions, DeviceVector, StackedVector, DeviceMatrix, SparseMatrix, spmv_t!, spmv_n!, to_dense!, DeviceBasis, DiagOperator, LowRankOperator, InequalityData, InequalityDecomp,
        InequalityDecompProject, ProjCGWork, DeviceConstraints, NR, ProjPenalty, ProjPenaltyWork, Euclidean, YRetract, ArmijoWork,
-       ExactLinesearchWork, LFPSQPParams, TerminationInfo, QuadLinearBallBox, SeparableLinearBallBox, ChainSeparableLinear, GraphPotentialLinear, like, edge_eval!, SparsePattern, set_values!, TridiagonalOperator, BandedOperator, DiagonalsOperator, SparseHessian, SparseOperator, SeparableElementwiseBox, ElementwiseConstraints,
+       ExactLinesearchWork, LFPSQPParams, TerminationInfo, QuadLinearBallBox, SeparableLinearBallBox, ChainSeparableLinear, GraphPotentialLinear, like, edge_eval!, SparseHessianPoints, points_info, pair_eval!, SparsePattern, set_values!, TridiagonalOperator, BandedOperator, DiagonalsOperator, SparseHessian, SparseOperator, SeparableElementwiseBox, ElementwiseConstraints,
        sin_system_constraints, sphere_system_constraints, clone, rowscale!, set_placement!, basis_and_vectors_placed, vectors_placed, placement_info, upload!, download, upload2!, download2, projcg!, retract!,
        retract_nr_batch!, pcg!, ProjPrecondition, ksvd!, armijo!, exact_linesearch!, optimize, optimize_core, hess_diag!, jac!, comm_unique_id, comm_init!, comm_p2p_export, comm_init_p2p!,
        shard_range, sync

@@ -188,6 +188,9 @@ _SIGS = {
     "lfpsqp_sphess_mul": [P, c_dbl, P, P, P, P],
     "lfpsqp_sphess_like": [P, P, C.POINTER(P)],
     "lfpsqp_sphess_edge_eval": [P, P, C.c_int, c_dbl, c_dbl, P, PD, P, P, P],
+    "lfpsqp_sphess_create_points": [P, c_i64, c_i64, C.c_int, c_i64, P, P, P, C.POINTER(P)],
+    "lfpsqp_sphess_points_info": [P, C.POINTER(c_i64), C.POINTER(c_i64)],
+    "lfpsqp_sphess_pair_eval": [P, P, C.c_int, c_dbl, c_dbl, P, PD, P, P, P],
     "lfpsqp_sphess_map_create": [P, P, c_i64, P, P, C.POINTER(P)],
     "lfpsqp_sphess_map_free": [P, P],
     "lfpsqp_sphess_map_info": [P, C.POINTER(c_i64), C.POINTER(c_i64), C.POINTER(c_i64)],

@@ -17,6 +17,8 @@ struct lfpsqp_sphess {
     int32_t* eidx = nullptr;        // [max(Ke, 1)][npad]
     double* eval = nullptr;
     mutable int* pattern_refs = nullptr;   // host counter of the handles on ridx / eidx; nullptr: this handle alone (never shared)
+    // lfpsqp_sphess_create_points: rows dim*p + c, c < dim, are the components of point p < npoints (sphess_pair.hip); 0 / 0 for every other handle
+    struct Points { int64_t npoints = 0; int dim = 0; } pts;
 };
 
 namespace lfpsqp {

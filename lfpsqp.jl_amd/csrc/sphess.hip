@@ -97,6 +97,56 @@ int lfpsqp_sphess_create(lfpsqp_ctx* ctx, int64_t n, int64_t nnz, const int64_t*
     return 0;
 }
 
+// Points with dim unknowns each, interleaved (row dim*p + c): a point edge becomes its dim^2 scalar entries, every point gets the dim (dim - 1) / 2
+// entries between its own components (value 0.0: the slot stays), and the builder above does the rest.
+int lfpsqp_sphess_create_points(lfpsqp_ctx* ctx, int64_t n, int64_t npoints, int dim, int64_t nedges, const int64_t* pi, const int64_t* pj,
+                                const double* w, lfpsqp_sphess** out) {
+    LF_ARG(ctx, ctx && out && npoints >= 0 && nedges >= 0 && (nedges == 0 || (pi && pj && w)));
+    *out = nullptr;
+    LF_ARG(ctx, dim == 2 || dim == 3);
+    if (npoints >= ((int64_t)1 << 31) / dim) return set_err(ctx, LFPSQP_ERR_UNSUPPORTED, "sphess: %lld points of %d unknowns (indices are stored as int32)", (long long)npoints, dim);
+    LF_ARG(ctx, n >= dim * npoints);
+    std::vector<std::pair<int64_t, int64_t>> pe((size_t)nedges);
+    for (int64_t e = 0; e < nedges; ++e) {
+        const int64_t p = pi[e], q = pj[e];
+        if (p < 0 || p >= npoints || q < 0 || q >= npoints) return set_err(ctx, LFPSQP_ERR_ARG, "sphess: point edge %lld out of range", (long long)e);
+        if (p == q) return set_err(ctx, LFPSQP_ERR_ARG, "sphess: point edge %lld joins a point to itself", (long long)e);
+        if (!std::isfinite(w[e])) return set_err(ctx, LFPSQP_ERR_ARG, "sphess: point edge %lld is not finite", (long long)e);
+        pe[(size_t)e] = {std::min(p, q), std::max(p, q)};
+    }
+    // the distinct neighbours of a point: its scalar rows hold dim of them each, and the dim - 1 entries of the point itself
+    std::sort(pe.begin(), pe.end());
+    pe.erase(std::unique(pe.begin(), pe.end()), pe.end());
+    std::vector<int32_t> deg((size_t)std::max<int64_t>(npoints, 1), 0);
+    int degmax = 0;
+    for (const auto& e : pe) degmax = std::max(degmax, std::max(++deg[(size_t)e.first], ++deg[(size_t)e.second]));
+    const int limit = (LFPSQP_SPHESS_MAX_ROW - (dim - 1)) / dim;
+    if (degmax > limit)
+        return set_err(ctx, LFPSQP_ERR_UNSUPPORTED, "sphess: a point with %d neighbours (> %d with %d unknowns per point: %d entries per row)", degmax, limit,
+                       dim, LFPSQP_SPHESS_MAX_ROW);
+    const size_t nnz = (size_t)nedges * (size_t)(dim * dim) + (size_t)npoints * (size_t)(dim * (dim - 1) / 2);
+    std::vector<int64_t> rows(nnz), cols(nnz);
+    std::vector<double> vals(nnz);
+    size_t z = 0;
+    for (int64_t p = 0; p < npoints; ++p)
+        for (int c = 0; c < dim; ++c)
+            for (int d = c + 1; d < dim; ++d, ++z) { rows[z] = dim * p + c; cols[z] = dim * p + d; vals[z] = 0.0; }
+    for (int64_t e = 0; e < nedges; ++e)             // (in the order given: every entry of a pair sums its duplicates in the same order, to the same bits)
+        for (int c = 0; c < dim; ++c)
+            for (int d = 0; d < dim; ++d, ++z) { rows[z] = dim * pi[e] + c; cols[z] = dim * pj[e] + d; vals[z] = w[e]; }
+    LF_TRY(lfpsqp_sphess_create(ctx, n, (int64_t)nnz, rows.data(), cols.data(), vals.data(), out));
+    (*out)->pts.npoints = npoints;
+    (*out)->pts.dim = dim;
+    return 0;
+}
+
+int lfpsqp_sphess_points_info(const lfpsqp_sphess* S, int64_t* npoints, int64_t* dim) {
+    if (!S) return LFPSQP_ERR_ARG;
+    if (npoints) *npoints = S->pts.npoints;
+    if (dim) *dim = S->pts.dim;
+    return 0;
+}
+
 int lfpsqp_sphess_free(lfpsqp_ctx* ctx, lfpsqp_sphess* S) {
     if (!S) return 0;
     if (ctx) (void)hipStreamSynchronize(ctx->stream);

@@ -1,0 +1,325 @@
+// lfpsqp_sphess_pair_eval: a PAIR potential between points of dim = 2 or 3 unknowns each,  scale * sum_e w_e psi(x_p - x_q)  over the point edges of
+// a handle made by lfpsqp_sphess_create_points (unknown dim*p + c = component c of point p) -- its value, its gradient, the diagonal and the values of
+// both ELL forms of a second handle on the same pattern, as lfpsqp_sphess_edge_eval does for one unknown per vertex (sphess_edge.hip).
+// With t = x_p - x_q, q = |t|^2:  grad psi = a t,  the Hessian block  B = a I + b (t t'):
+//   kind 0: psi = q/2                                 a = 1          b = 0
+//   kind 1: psi = (r - l)^2 / 2,  r = sqrt(q)         a = 1 - l/r    b = l / (r q)                         (a spring of rest length l = delta)
+//   kind 2: psi = q / (s + 1),  s = sqrt(1 + q/d^2)   a = 1/s        b = -(1/d^2) / (s (1 + q/d^2))        (radial pseudo-Huber, d = delta)
+// Stored values: -(scale w)(a [c == c'] + b (t_c t_c')) at ((p,c),(q,c')), scale * sum_q w_pq b (t_c t_c') at the intra-point entry ((p,c),(p,c')).
+//
+// LANES OWN SCALAR ROWS, two per lane (i, i + 1), as every functor of sphess_edge.hip: the ELL arrays are laid out by scalar row, so the index,
+// weight and value of a slot are one aligned 8 / 16 / 16-byte access per lane and consecutive lanes are coalesced, run_vec and its pad-row rule apply
+// unchanged, and grad / diag are one 16-byte read-modify-write.  In 2-D the pair (i, i + 1) IS a point, in 3-D it is not; either way each row runs its
+// own walk, so the square root and the division of a neighbour are computed once per ROW, dim times per point.  The other choice, a lane per point
+// (dim rows of dim*deg + dim - 1 slots: strided 8-byte accesses in 3-D, dim times the registers, a launcher of its own) is not built: FINDINGS.md 23.
+//
+// A row's slots are in increasing index order, so the dim slots of a neighbour q are consecutive and start at its component 0: (a, b) and t are
+// computed at that slot and kept for the next dim - 1.  The slots of the point itself (dim - 1 of them, between the lower and the higher neighbours)
+// are written after the walk from their sums; an empty slot holds the row itself and is left alone.  Rows >= dim*npoints (a slack row) and the pad
+// row behind an odd n have no couplings and are skipped.
+// BITS.  t_c t_c' is formed first and multiplied by b afterwards; (-t_c)(-t_c') and commutativity give the row (q,c') the bits of the row (p,c); q is
+// an fma chain over the components in order (even in t); both rows of an intra-point pair walk the same neighbours in the same order.  The edge
+// form recomputes a cross-point entry from its owner's side with the same expressions, and COPIES an intra-point entry from the row form of H that
+// the row kernel has just written (found by searching the owner's row for the partner).  Every fma is written out: no contraction is relied on.
+// ROUNDINGS per value (a count k stands for gamma_k; t_c = fl(x_pc - x_qc) 1, against the exact difference; tests/test_sphess_pair.py holds the
+// kernels to these), cq = dim + 2 for q (t_c^2 carries 3, each further fma one more):
+//   kind 1: r = sqrt(q): cr = ceil(cq / 2) + 1 = 3 / 4 (2-D / 3-D).  psi = ((r - l)(r - l)) / 2: 2 cr + 3 = 9 / 11 on (r + l)^2 / 2.  a = 1 - l/r: cr + 2 =
+//           5 / 6 on 1 + l/r.  b = l / (r q): cr + cq + 2 = 9 / 11.
+//   kind 2 (1/d^2 on the host: 2): u = fma(q, 1/d^2, 1): cq + 3 = 7 / 8.  s = sqrt(u): ceil((cq + 3) / 2) + 1 = 5.  psi = q / (s + 1): cq + 7 = 11 / 12.
+//           a = 1/s: 6.  b = -(1/d^2) / (s u): 2 + (5 + cq + 3 + 1) + 1 = cq + 12 = 16 / 17.
+//   v = a [c == c'] + b (t_c t_c') (one fma, or one product; t_c t_c' carries 3): cv = count(b) + 4 = 13 / 15 (kind 1) and 20 / 21 (kind 2), on
+//           |a|-terms [c == c'] + |b t_c t_c'|, the |a|-terms being 1 + l/r (kind 1) and a (kind 2).
+//   a stored cross-point value: fl(scale w) and the product: cv + 2.  grad term a t_c: count(a) + 2.
+//   a row sum (grad, diag, an intra-point entry): at most deg additions of the fma chain (one per neighbour) and one rounding with scale:
+//           deg + count(a) + 3 (grad), deg + cv + 1 (diag, intra-point).   f: as in sphess_edge.hip, npoints deg + count(psi) + 1.
+#include <math.h>
+
+#include "sphess.h"
+
+namespace lfpsqp {
+
+template <int KIND>
+struct PairPot {
+    double delta;              // l (kind 1)
+    double rd2;                // 1 / delta^2 (kind 2)
+    // (psi, a, b) at q = |t|^2
+    __device__ __forceinline__ void eval(double q, double& psi, double& a, double& b) const {
+        if (KIND == 0) {
+            psi = 0.5 * q; a = 1.0; b = 0.0;
+        } else if (KIND == 1) {
+            const double r = sqrt(q), e = r - delta;
+            psi = 0.5 * (e * e); a = 1.0 - delta / r; b = delta / (r * q);
+        } else {
+            const double u = fma(q, rd2, 1.0), s = sqrt(u);
+            psi = q / (s + 1.0); a = 1.0 / s; b = -(rd2 / (s * u));
+        }
+    }
+};
+
+__device__ __forceinline__ double sel(bool c, double a, double b) { return c ? a : b; }
+
+template <int DIM>
+__device__ __forceinline__ double pick(int c, double t0, double t1, double t2) {
+    return c == 0 ? t0 : (DIM == 2 || c == 1) ? t1 : t2;
+}
+
+// t = x_p - x_q for the neighbour point at index j0 (its component 0) and q = |t|^2
+template <int DIM>
+__device__ __forceinline__ double diff(const double* x, double xp0, double xp1, double xp2, int32_t j0, double& t0, double& t1, double& t2) {
+    t0 = xp0 - x[j0];
+    t1 = xp1 - x[j0 + 1];
+    double q = fma(t1, t1, t0 * t0);
+    if (DIM == 3) { t2 = xp2 - x[j0 + 2]; q = fma(t2, t2, q); }
+    else t2 = 0.0;
+    return q;
+}
+
+// One scalar row's walk over its slots (row form).  The state is named, not indexed: no array that the compiler could put into scratch.
+template <int DIM, int KIND, bool WF, bool WV>
+struct PairRow {
+    int32_t r;                 // the row, dim*p + c
+    int32_t base;              // dim*p
+    int c;
+    bool on;                   // a row of a point (not a slack row, not a pad row)
+    double xp0, xp1, xp2;
+    double t0, t1, t2, tc, a, b;
+    double e, g, d, m0, m1;
+    int kin;                   // the first slot of the point itself; -1: not met yet
+
+    __device__ __forceinline__ void init(int64_t row, bool valid, int64_t nrows, const double* x) {
+        on = valid && row < nrows;
+        r = (int32_t)row;
+        const int32_t p = r / DIM;
+        base = p * DIM;
+        c = r - base;
+        xp0 = xp1 = xp2 = 0.0;
+        if (on) {
+            xp0 = x[base]; xp1 = x[base + 1];
+            if (DIM == 3) xp2 = x[base + 2];
+        }
+        t0 = t1 = t2 = tc = a = b = 0.0;
+        e = g = d = m0 = m1 = 0.0;
+        kin = -1;
+    }
+    // slot k holding (j, w): true and the new value in h when the slot is a cross-point entry
+    __device__ __forceinline__ bool slot(const PairPot<KIND>& pot, const double* x, double scale, int k, int32_t j, double w, double& h) {
+        if (!on) return false;
+        const int32_t jb = (j / DIM) * DIM;
+        if (jb == base) {                           // the row itself (an empty slot) or another component of its point
+            if (j != r && kin < 0) kin = k;
+            return false;
+        }
+        const int cc = j - jb;
+        if (cc == 0) {
+            const double q = diff<DIM>(x, xp0, xp1, xp2, j, t0, t1, t2);
+            double psi;
+            pot.eval(q, psi, a, b);
+            tc = pick<DIM>(c, t0, t1, t2);
+            if (WF && c == 0) e = fma(w, psi, e);   // (the point's energy, once: at its component 0)
+            if (WV) g = fma(w, a * tc, g);
+        }
+        double v;
+        if (KIND == 0) v = cc == c ? 1.0 : 0.0;
+        else {
+            const double tt = tc * pick<DIM>(cc, t0, t1, t2);
+            v = cc == c ? fma(b, tt, a) : b * tt;
+        }
+        if (WV) {
+            // one fma into d (cc == c) or into the sum of the point's other components, in increasing order m0, m1 -- selected BY VALUE (sel: its
+            // arguments are loaded first).  Three conditional updates, or ?: between the members themselves (an lvalue), become one update through a
+            // pointer into this object, and the object then lives in scratch.
+            const int k3 = cc == c ? 0 : (DIM == 2 || cc == (c == 0 ? 1 : 0)) ? 1 : 2;
+            const double s = fma(w, v, sel(k3 == 0, d, sel(k3 == 1, m0, m1)));
+            d = sel(k3 == 0, s, d);
+            m0 = sel(k3 == 1, s, m0);
+            m1 = sel(k3 == 2, s, m1);
+        }
+        h = KIND == 0 && cc != c ? 0.0 : -((scale * w) * v);
+        return true;
+    }
+    // the intra-point slots, from their sums
+    __device__ __forceinline__ void intra(double scale, double* hval, int64_t npad) const {
+        if (!on || kin < 0) return;
+        double* hp = hval + (int64_t)kin * npad + r;
+        hp[0] = KIND == 0 ? 0.0 : scale * m0;
+        if (DIM == 3) hp[npad] = KIND == 0 ? 0.0 : scale * m1;
+    }
+};
+
+// Row form, two rows per lane.  WF: the energy goes to the reduction (every point edge is seen from both ends, at component 0 of either: the host
+// halves the sum); WV: grad / diag / hval, each optional.  <WF, !WV> writes nothing.  The slot loop is rolled for every kind, as the scalar kinds
+// 1 and 2 (FINDINGS.md 23 has the resource report).
+template <int DIM, int KIND, bool WF, bool WV>
+struct PairRowF {
+    PairPot<KIND> pot;
+    const int32_t* idx;
+    const double* w;
+    int64_t npad;
+    int K;
+    int64_t nrows;             // dim * npoints
+    const double* x;
+    double scale;
+    double* grad;
+    double* diag;
+    double* hval;
+    __device__ __forceinline__ bool skip() const { return false; }
+    __device__ __forceinline__ void apply(int64_t i, bool v0, bool v1, double* red) const {
+        if (!v0 || i >= nrows) return;
+        PairRow<DIM, KIND, WF, WV> r0, r1;
+        r0.init(i, v0, nrows, x);
+        r1.init(i + 1, v1, nrows, x);
+        const int32_t* ip = idx + i;
+        const double* wp = w + i;
+#pragma unroll 1
+        for (int k = 0; k < K; ++k) {
+            const int64_t o = (int64_t)k * npad;
+            const int2 jj = *reinterpret_cast<const int2*>(ip + o);
+            const double2 ww = ld2(wp + o);
+            double h0 = 0.0, h1 = 0.0;
+            const bool s0 = r0.slot(pot, x, scale, k, jj.x, ww.x, h0);
+            const bool s1 = r1.slot(pot, x, scale, k, jj.y, ww.y, h1);
+            if (WV && hval) {
+                if (s0 && s1) st2(hval + i + o, make_double2(h0, h1));
+                else if (s0) hval[i + o] = h0;
+                else if (s1) hval[i + 1 + o] = h1;
+            }
+        }
+        if (WF) red[0] += r0.e + r1.e;
+        if (WV) {
+            if (hval) { r0.intra(scale, hval, npad); r1.intra(scale, hval, npad); }
+            if (grad) {
+                if (r1.on) { const double2 s = ld2(grad + i); st2(grad + i, make_double2(fma(scale, r0.g, s.x), fma(scale, r1.g, s.y))); }
+                else grad[i] = fma(scale, r0.g, grad[i]);
+            }
+            if (diag) {
+                if (r1.on) { const double2 s = ld2(diag + i); st2(diag + i, make_double2(fma(scale, r0.d, s.x), fma(scale, r1.d, s.y))); }
+                else diag[i] = fma(scale, r0.d, diag[i]);
+            }
+        }
+    }
+};
+
+// One slot of the edge form at owner row `row`: partner j, weight w.  A cross-point entry is the row kernel's expression from the owner's side; an
+// intra-point entry is copied from the owner's row of H's row form (at most dim - 1 such slots in a row; the row kernel ran before).
+template <int DIM, int KIND>
+__device__ __forceinline__ bool pair_own_slot(const PairPot<KIND>& pot, const double* x, double scale, const int32_t* ridx, const double* hrow, int64_t npad,
+                                              int Kr, int64_t row, bool valid, int64_t nrows, int32_t j, double w, double& h) {
+    if (!valid || row >= nrows) return false;
+    const int32_t r = (int32_t)row, base = (r / DIM) * DIM, jb = (j / DIM) * DIM;
+    if (jb == base) {
+        if (j == r) return false;                   // an empty slot
+        h = 0.0;
+#pragma unroll 1
+        for (int k = 0; k < Kr; ++k)
+            if (ridx[(int64_t)k * npad + r] == j) { h = hrow[(int64_t)k * npad + r]; break; }
+        return true;
+    }
+    const int c = r - base, cc = j - jb;
+    if (KIND == 0) {
+        h = cc == c ? -(scale * w) : 0.0;
+        return true;
+    }
+    double t0, t1, t2, psi, a, b;
+    const double q = diff<DIM>(x, x[base], x[base + 1], DIM == 3 ? x[base + 2] : 0.0, jb, t0, t1, t2);
+    pot.eval(q, psi, a, b);
+    const double tt = pick<DIM>(c, t0, t1, t2) * pick<DIM>(cc, t0, t1, t2);
+    const double v = cc == c ? fma(b, tt, a) : b * tt;
+    h = -((scale * w) * v);
+    return true;
+}
+
+template <int DIM, int KIND>
+struct PairOwnF {
+    PairPot<KIND> pot;
+    const int32_t* idx;        // the edge form
+    const double* w;
+    int64_t npad;
+    int K;
+    const int32_t* ridx;       // the row form: the pattern, and H's values
+    const double* hrow;
+    int Kr;
+    int64_t nrows;
+    const double* x;
+    double scale;
+    double* hval;
+    __device__ __forceinline__ bool skip() const { return false; }
+    __device__ __forceinline__ void apply(int64_t i, bool v0, bool v1, double*) const {
+        if (!v0 || i >= nrows) return;
+        const int32_t* ip = idx + i;
+        const double* wp = w + i;
+#pragma unroll 1
+        for (int k = 0; k < K; ++k) {
+            const int64_t o = (int64_t)k * npad;
+            const int2 jj = *reinterpret_cast<const int2*>(ip + o);
+            const double2 ww = ld2(wp + o);
+            double h0 = 0.0, h1 = 0.0;
+            const bool s0 = pair_own_slot<DIM, KIND>(pot, x, scale, ridx, hrow, npad, Kr, i, v0, nrows, jj.x, ww.x, h0);
+            const bool s1 = pair_own_slot<DIM, KIND>(pot, x, scale, ridx, hrow, npad, Kr, i + 1, v1, nrows, jj.y, ww.y, h1);
+            if (s0 && s1) st2(hval + i + o, make_double2(h0, h1));
+            else if (s0) hval[i + o] = h0;
+            else if (s1) hval[i + 1 + o] = h1;
+        }
+    }
+};
+
+template <int DIM, int KIND>
+static int pair_eval_kind(lfpsqp_ctx* ctx, const lfpsqp_sphess* W, double delta, double rd2, double scale, const double* x, bool wantf, double* grad,
+                          double* diag, lfpsqp_sphess* H) {
+    const PairPot<KIND> pot{delta, rd2};
+    const int64_t nrows = (int64_t)DIM * W->pts.npoints;
+    const bool wv = grad || diag || H;
+    double* red = ctx->scal + 32;
+    if (wantf && !wv)
+        return run_vec<PairRowF<DIM, KIND, true, false>, 1, NoPost>(
+            ctx, W->n, PairRowF<DIM, KIND, true, false>{pot, W->ridx, W->rval, W->npad, W->Kr, nrows, x, scale, nullptr, nullptr, nullptr}, 0u, red, NoPost());
+    double* hr = H ? H->rval : nullptr;
+    if (wantf)
+        LF_TRY((run_vec<PairRowF<DIM, KIND, true, true>, 1, NoPost>(
+            ctx, W->n, PairRowF<DIM, KIND, true, true>{pot, W->ridx, W->rval, W->npad, W->Kr, nrows, x, scale, grad, diag, hr}, 0u, red, NoPost())));
+    else
+        LF_TRY((run_vec<PairRowF<DIM, KIND, false, true>, 0, NoPost>(
+            ctx, W->n, PairRowF<DIM, KIND, false, true>{pot, W->ridx, W->rval, W->npad, W->Kr, nrows, x, scale, grad, diag, hr}, 0u, nullptr, NoPost())));
+    if (H && W->Ke > 0)
+        LF_TRY((run_vec<PairOwnF<DIM, KIND>, 0, NoPost>(
+            ctx, W->n, PairOwnF<DIM, KIND>{pot, W->eidx, W->eval, W->npad, W->Ke, W->ridx, H->rval, W->Kr, nrows, x, scale, H->eval}, 0u, nullptr, NoPost())));
+    return 0;
+}
+
+template <int DIM>
+static int pair_eval_dim(lfpsqp_ctx* ctx, const lfpsqp_sphess* W, int kind, double delta, double rd2, double scale, const double* x, bool wantf,
+                         double* grad, double* diag, lfpsqp_sphess* H) {
+    if (kind == 0) return pair_eval_kind<DIM, 0>(ctx, W, delta, rd2, scale, x, wantf, grad, diag, H);
+    if (kind == 1) return pair_eval_kind<DIM, 1>(ctx, W, delta, rd2, scale, x, wantf, grad, diag, H);
+    return pair_eval_kind<DIM, 2>(ctx, W, delta, rd2, scale, x, wantf, grad, diag, H);
+}
+
+}  // namespace lfpsqp
+
+using namespace lfpsqp;
+
+extern "C" int lfpsqp_sphess_pair_eval(lfpsqp_ctx* ctx, const lfpsqp_sphess* W, int kind, double delta, double scale, const lfpsqp_vec* x, double* f,
+                                       lfpsqp_vec* grad, lfpsqp_vec* diag, lfpsqp_sphess* H) {
+    LF_ARG(ctx, ctx && W && x && kind >= 0 && kind <= 2 && std::isfinite(scale));
+    LF_ARG(ctx, W->pts.dim == 2 || W->pts.dim == 3);             // a handle of lfpsqp_sphess_create_points (or a handle on its pattern)
+    const int64_t nrows = (int64_t)W->pts.dim * W->pts.npoints;
+    LF_ARG(ctx, x->n >= nrows);
+    LF_ARG(ctx, kind != 1 || (std::isfinite(delta) && delta >= 0.0));
+    LF_ARG(ctx, kind != 2 || (std::isfinite(delta) && delta > 0.0));
+    LF_ARG(ctx, (!grad || (grad->n >= nrows && grad->p != x->p)) && (!diag || (diag->n >= nrows && diag->p != x->p)) && (!grad || !diag || grad->p != diag->p));
+    // H: another handle on W's pattern (W itself would lose the weights it is evaluated from)
+    LF_ARG(ctx, !H || (H != W && H->ridx == W->ridx && H->eidx == W->eidx && H->rval != W->rval));
+    if (ctx->comm_active())        // (a rank sees its own rows only: the edges across the shard boundaries would silently drop out)
+        return set_err(ctx, LFPSQP_ERR_UNSUPPORTED, "lfpsqp_sphess_pair_eval: one rank only (no halo exchange between row shards)");
+    if (f) *f = 0.0;
+    if (nrows == 0 || !(f || grad || diag || H)) return 0;
+    const double rd2 = kind == 2 ? 1.0 / (delta * delta) : 0.0;
+    double *gp = grad ? grad->p : nullptr, *dp = diag ? diag->p : nullptr;
+    if (W->pts.dim == 2) LF_TRY(pair_eval_dim<2>(ctx, W, kind, delta, rd2, scale, x->p, f != nullptr, gp, dp, H));
+    else LF_TRY(pair_eval_dim<3>(ctx, W, kind, delta, rd2, scale, x->p, f != nullptr, gp, dp, H));
+    if (f) {
+        double s = 0.0;
+        LF_TRY(read_back(ctx, ctx->scal + 32, &s, 1));
+        *f = scale * (0.5 * s);
+    }
+    return 0;
+}

@@ -523,6 +523,55 @@ class GraphPotentialLinear(SeparableLinearBallBox):
         self._edge(x, diag=hx, out=self.sparse_hessian)
 
 
+class PointPotentialLinear(SeparableLinearBallBox):
+    """A separable objective plus a PAIR potential between points of ``dim`` = 2 or 3 unknowns each: the n = dim*npoints variables are interleaved
+    (x[dim*p + c] is component c of point p) and f(x) = sum_i phi(x_i - c_i; a_i) + kappa sum_e w_e psi(x_p - x_q; delta) over the undirected
+    edges ``edges = (pi, pj, w)`` between POINTS -- ``pair_kind`` 0: psi = |t|^2/2, 1: (|t| - delta)^2/2 (a spring of rest length ``delta``: truss
+    and spring networks, graph layout, sensor localisation), 2: the radial pseudo-Huber function delta^2 (sqrt(1 + |t|^2/delta^2) - 1)
+    (vector-valued edge-preserving smoothing) -- under the constraint set of :class:`GraphPotentialLinear` (dense linear equalities, optional ball
+    with its slack row, optional box), of which this class has the shape line for line.  Every edge contributes a dense dim x dim block
+    a I + b t t' to the Lagrangian Hessian, every point the entries between its own components, and all of them change with x: ``weights``
+    (:meth:`SparseHessian.from_points`, N rows, never modified) holds w, ``sparse_hessian`` = ``weights.like()`` the current entries, rewritten
+    with the diagonal by ``diag_objective_`` / ``diag_`` in one device call (lfpsqp_sphess_pair_eval) before every truncated-Newton solve, which
+    ``optimize`` then runs as a :class:`SparseOperator` on lfpsqp_projcg_sparse.  At most 15 neighbours per point in 2-D, 10 in 3-D.  Kind 1 is
+    not convex where an edge is shorter than its rest length, and singular where two joined points coincide.  One rank."""
+
+    def __init__(self, ctx: Context, npoints: int, dim: int, m: int, Jct: DeviceMatrix, b, kind: int, a, c=0.0, edges=None, kappa: float = 1.0,
+                 pair_kind: int = 2, delta: float = 1.0, **kw):
+        n = int(dim) * int(npoints)
+        assert kw.get("n_global", n) in (None, n), "graph objective: one rank (the couplings would cross the shard boundaries)"
+        assert edges is not None and len(edges) == 3, "point objective: edges = (pi, pj, w)"
+        assert int(dim) in (2, 3), "point objective: dim 2 or 3"
+        assert int(pair_kind) in (0, 1, 2), "point objective: pair_kind 0 .. 2"
+        super().__init__(ctx, n, m, Jct, b, kind, a, c, **kw)
+        from .projcg import SparseHessian
+        self.npoints, self.dim = int(npoints), int(dim)
+        self.kappa, self.pair_kind, self.delta = float(kappa), int(pair_kind), float(delta)
+        ei, ej = (np.asarray(e, dtype=np.int64).ravel() for e in edges[:2])
+        assert ei.shape == ej.shape and np.all((0 <= ei) & (ei < npoints) & (0 <= ej) & (ej < npoints)), "point objective: edges between the points"
+        w = np.broadcast_to(np.asarray(edges[2], dtype=np.float64), ei.shape)
+        self.weights = SparseHessian.from_points(ctx, self.N, self.npoints, self.dim, ei, ej, w)   # N rows: the slack row, when the ball is there, has no edges
+        self.sparse_hessian = self.weights.like()
+
+    def _pair(self, x, grad=None, diag=None, out=None, want_f=False):
+        return self.weights.pair_eval(self.pair_kind, self.delta, self.kappa, x, grad, diag, out, want_f)
+
+    def f(self, x: DeviceVector) -> float:
+        return super().f(x) + self._pair(x, want_f=True)
+
+    def grad_(self, g: DeviceVector, x: DeviceVector):
+        super().grad_(g, x)
+        self._pair(x, grad=g)
+
+    def diag_objective_(self, hx: DeviceVector, x: DeviceVector):
+        super().diag_objective_(hx, x)
+        self._pair(x, diag=hx, out=self.sparse_hessian)
+
+    def diag_(self, hx: DeviceVector, x: DeviceVector, lam: np.ndarray):
+        super().diag_(hx, x, lam)
+        self._pair(x, diag=hx, out=self.sparse_hessian)
+
+
 class SeparableElementwiseBox(SeparableLinearBallBox):
     """The device-resident problem class with NONLINEAR equality constraints: a separable objective
     (``kind`` / ``a`` / ``c`` as in :class:`SeparableLinearBallBox`) under ``cons``, an :class:`ElementwiseConstraints`

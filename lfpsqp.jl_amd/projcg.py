@@ -224,9 +224,36 @@ class SparseHessian:
         h = C.c_void_p()
         ctx.check(ctx.L.lfpsqp_sphess_create(ctx.h, int(n), ii.size, ii.ctypes.data, jj.ctypes.data, ww.ctypes.data, C.byref(h)))
         self.h = h
-        out = [_capi.c_i64() for _ in range(4)]
-        ctx.check(ctx.L.lfpsqp_sphess_info(self.h, *(C.byref(o) for o in out)))
-        self.n, self.nedges, self.row_width, self.edge_width = (o.value for o in out)
+        self._read_info()
+
+    def _read_info(self):
+        ctx = self.ctx
+        out = [_capi.c_i64() for _ in range(6)]
+        ctx.check(ctx.L.lfpsqp_sphess_info(self.h, *(C.byref(o) for o in out[:4])))
+        ctx.check(ctx.L.lfpsqp_sphess_points_info(self.h, *(C.byref(o) for o in out[4:])))
+        self.n, self.nedges, self.row_width, self.edge_width, self.npoints, self.dim = (o.value for o in out)
+
+    @classmethod
+    def from_points(cls, ctx: Context, n: int, npoints: int, dim: int, pi, pj, w) -> "SparseHessian":
+        """The handle of a PAIR term between ``npoints`` points of ``dim`` = 2 or 3 unknowns each, interleaved (unknown ``dim*p + c`` is component
+        c of point p; lfpsqp_sphess_create_points): ``(pi, pj, w)`` are undirected edges between points (0-based, any order, ``w`` a scalar or one
+        weight per edge; duplicates add up), every edge a dense dim x dim block of entries holding w, every point the entries between its own
+        components holding 0.0.  ``n`` >= dim*npoints rows; the rows behind the points (a slack row) carry no couplings.  At most 15 neighbours
+        per point in 2-D and 10 in 3-D (32 entries per scalar row).  ``npoints`` and ``dim`` are kept (0 for every other handle; :meth:`like`
+        copies them); :meth:`pair_eval` evaluates the term."""
+        import numpy as np
+        ii = np.ascontiguousarray(np.asarray(pi, dtype=np.int64).ravel())
+        jj = np.ascontiguousarray(np.asarray(pj, dtype=np.int64).ravel())
+        if ii.shape != jj.shape:
+            raise ValueError("SparseHessian.from_points: pi and pj of the same length")
+        ww = np.ascontiguousarray(np.broadcast_to(np.asarray(w, dtype=np.float64), ii.shape))
+        h = C.c_void_p()
+        ctx.check(ctx.L.lfpsqp_sphess_create_points(ctx.h, int(n), int(npoints), int(dim), ii.size, ii.ctypes.data, jj.ctypes.data, ww.ctypes.data,
+                                                    C.byref(h)))
+        S = object.__new__(cls)
+        S.ctx, S.h = ctx, h
+        S._read_info()
+        return S
 
     def like(self) -> "SparseHessian":
         """A second handle on the same pattern (lfpsqp_sphess_like): the index arrays are shared, the values are its own, initialised to this
@@ -236,9 +263,7 @@ class SparseHessian:
         ctx.check(ctx.L.lfpsqp_sphess_like(ctx.h, self.h, C.byref(h)))
         H = object.__new__(SparseHessian)
         H.ctx, H.h = ctx, h
-        out = [_capi.c_i64() for _ in range(4)]
-        ctx.check(ctx.L.lfpsqp_sphess_info(H.h, *(C.byref(o) for o in out)))
-        H.n, H.nedges, H.row_width, H.edge_width = (o.value for o in out)
+        H._read_info()
         return H
 
     def edge_eval(self, kind: int, delta: float, scale: float, x, grad=None, diag=None, out=None, want_f: bool = True):
@@ -252,6 +277,23 @@ class SparseHessian:
             raise ValueError("SparseHessian.edge_eval: the output handle belongs to another context")
         f = C.c_double()
         ctx.check(ctx.L.lfpsqp_sphess_edge_eval(ctx.h, self.h, int(kind), float(delta), float(scale), x.h, C.byref(f) if want_f else None,
+                                                grad.h if grad is not None else None, diag.h if diag is not None else None,
+                                                out.h if out is not None else None))
+        return f.value if want_f else None
+
+    def pair_eval(self, kind: int, delta: float, scale: float, x, grad=None, diag=None, out=None, want_f: bool = True):
+        """The pair term scale * sum_e w_e psi(x_p - x_q) between the points of a handle made by :meth:`from_points`, with this handle's values as
+        the weights (lfpsqp_sphess_pair_eval; t = x_p - x_q in R^dim, ``kind`` 0: |t|^2/2, 1: (|t| - delta)^2/2, a spring of rest length
+        ``delta``, 2: the radial pseudo-Huber function delta^2 (sqrt(1 + |t|^2/delta^2) - 1)).  The conventions are those of :meth:`edge_eval`:
+        the value is returned (None with ``want_f=False``), the gradient is ADDED to ``grad`` and the Hessian's diagonal to ``diag`` (their first
+        dim*npoints entries; ``x`` may be longer), and ``out``, a handle made by :meth:`like`, receives the off-diagonal entries: the dim x dim
+        block -(scale w)(a I + b t t') per edge and the entries between a point's own components.  This handle is never modified.  Kind 1 with
+        two coincident points joined by an edge is a singularity of the potential: the outputs are then not finite."""
+        ctx = self.ctx
+        if out is not None and out.ctx is not ctx:
+            raise ValueError("SparseHessian.pair_eval: the output handle belongs to another context")
+        f = C.c_double()
+        ctx.check(ctx.L.lfpsqp_sphess_pair_eval(ctx.h, self.h, int(kind), float(delta), float(scale), x.h, C.byref(f) if want_f else None,
                                                 grad.h if grad is not None else None, diag.h if diag is not None else None,
                                                 out.h if out is not None else None))
         return f.value if want_f else None
