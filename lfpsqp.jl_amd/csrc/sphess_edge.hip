@@ -35,7 +35,7 @@ struct EdgePot {
 // indices, weights and x and writes nothing.  Empty slots (the row itself, weight 0) have t = 0 and add 0; the pad row behind an odd n is computed
 // and dropped.  The slot loop is unrolled by four for kind 0, as SpHessD::couple, and rolled for the other kinds: unrolled, the two rows' division and
 // square-root sequences take 100 .. 124 VGPRs (4 waves per SIMD); rolled 46 .. 68 (7 or 8, like DiagsMulF<SpHessD>), no scratch either way.
-template <int KIND, bool WF, bool WV>
+template <bool WF, bool WV, int KIND>
 struct EdgeRowF {
     EdgePot<KIND> pot;
     const int32_t* idx;
@@ -69,21 +69,14 @@ struct EdgeRowF {
                 d0 = fma(ww.x, c0, d0); d1 = fma(ww.y, c1, d1);
                 if (hval) {
                     const double h0 = -((scale * ww.x) * c0), h1 = -((scale * ww.y) * c1);
-                    if (v1) st2(hval + i + o, make_double2(h0, h1));
-                    else hval[i + o] = h0;
+                    store_rows(hval, i, o, v1, h0, h1);
                 }
             }
         }
         if (WF) red[0] += e0 + (v1 ? e1 : 0.0);
         if (WV) {
-            if (grad) {
-                if (v1) { const double2 r = ld2(grad + i); st2(grad + i, make_double2(fma(scale, g0, r.x), fma(scale, g1, r.y))); }
-                else grad[i] = fma(scale, g0, grad[i]);
-            }
-            if (diag) {
-                if (v1) { const double2 r = ld2(diag + i); st2(diag + i, make_double2(fma(scale, d0, r.x), fma(scale, d1, r.y))); }
-                else diag[i] = fma(scale, d0, diag[i]);
-            }
+            if (grad) add_rows(grad, i, v1, scale, g0, g1);
+            if (diag) add_rows(diag, i, v1, scale, d0, d1);
         }
     }
 };
@@ -115,6 +108,7 @@ struct EdgeOwnF {
             pot.eval(t0, t0 * t0, a0, b0, c0);
             pot.eval(t1, t1 * t1, a1, b1, c1);
             const double h0 = -((scale * ww.x) * c0), h1 = -((scale * ww.y) * c1);
+            // (store_rows, written out: through the helper the compiler issues this loop's loads of kinds 0 and 1 in another order)
             if (v1) st2(hval + i + o, make_double2(h0, h1));
             else hval[i + o] = h0;
         }
@@ -125,22 +119,8 @@ template <int KIND>
 static int edge_eval_kind(lfpsqp_ctx* ctx, const lfpsqp_sphess* W, double rd2, double scale, const double* x, bool wantf, double* grad, double* diag,
                           lfpsqp_sphess* H) {
     const EdgePot<KIND> pot{rd2};
-    const bool wv = grad || diag || H;
-    double* red = ctx->scal + 32;
-    if (wantf && !wv)
-        return run_vec<EdgeRowF<KIND, true, false>, 1, NoPost>(
-            ctx, W->n, EdgeRowF<KIND, true, false>{pot, W->ridx, W->rval, W->npad, W->Kr, x, scale, nullptr, nullptr, nullptr}, 0u, red, NoPost());
-    double* hr = H ? H->rval : nullptr;
-    if (wantf)
-        LF_TRY((run_vec<EdgeRowF<KIND, true, true>, 1, NoPost>(
-            ctx, W->n, EdgeRowF<KIND, true, true>{pot, W->ridx, W->rval, W->npad, W->Kr, x, scale, grad, diag, hr}, 0u, red, NoPost())));
-    else
-        LF_TRY((run_vec<EdgeRowF<KIND, false, true>, 0, NoPost>(
-            ctx, W->n, EdgeRowF<KIND, false, true>{pot, W->ridx, W->rval, W->npad, W->Kr, x, scale, grad, diag, hr}, 0u, nullptr, NoPost())));
-    if (H && W->Ke > 0)
-        LF_TRY((run_vec<EdgeOwnF<KIND>, 0, NoPost>(ctx, W->n, EdgeOwnF<KIND>{pot, W->eidx, W->eval, W->npad, W->Ke, x, scale, H->eval}, 0u, nullptr,
-                                                   NoPost())));
-    return 0;
+    return eval_launch<EdgeRowF, KIND>(ctx, W, wantf, grad, diag, H, EdgeOwnF<KIND>{pot, W->eidx, W->eval, W->npad, W->Ke, x, scale, H ? H->eval : nullptr},
+                                       pot, W->ridx, W->rval, W->npad, W->Kr, x, scale);
 }
 
 }  // namespace lfpsqp
@@ -149,24 +129,14 @@ using namespace lfpsqp;
 
 extern "C" int lfpsqp_sphess_edge_eval(lfpsqp_ctx* ctx, const lfpsqp_sphess* W, int kind, double delta, double scale, const lfpsqp_vec* x, double* f,
                                        lfpsqp_vec* grad, lfpsqp_vec* diag, lfpsqp_sphess* H) {
-    LF_ARG(ctx, ctx && W && x && kind >= 0 && kind <= 2 && std::isfinite(scale) && x->n >= W->n);
+    LF_ARG(ctx, ctx && W && x && kind >= 0 && kind <= 2 && std::isfinite(scale));
     LF_ARG(ctx, kind != 2 || (std::isfinite(delta) && delta > 0.0));
-    LF_ARG(ctx, (!grad || (grad->n >= W->n && grad->p != x->p)) && (!diag || (diag->n >= W->n && diag->p != x->p)) && (!grad || !diag || grad->p != diag->p));
-    // H: another handle on W's pattern (W itself would lose the weights it is evaluated from)
-    LF_ARG(ctx, !H || (H != W && H->ridx == W->ridx && H->eidx == W->eidx && H->rval != W->rval));
-    if (ctx->comm_active())        // (a rank sees its own rows only: the edges across the shard boundaries would silently drop out)
-        return set_err(ctx, LFPSQP_ERR_UNSUPPORTED, "lfpsqp_sphess_edge_eval: one rank only (no halo exchange between row shards)");
-    if (f) *f = 0.0;
+    LF_TRY(eval_check(ctx, "lfpsqp_sphess_edge_eval", W, W->n, x, f, grad, diag, H));
     if (W->n == 0 || !(f || grad || diag || H)) return 0;
     const double rd2 = kind == 2 ? 1.0 / (delta * delta) : 0.0;
     double *gp = grad ? grad->p : nullptr, *dp = diag ? diag->p : nullptr;
     if (kind == 0) LF_TRY(edge_eval_kind<0>(ctx, W, rd2, scale, x->p, f != nullptr, gp, dp, H));
     else if (kind == 1) LF_TRY(edge_eval_kind<1>(ctx, W, rd2, scale, x->p, f != nullptr, gp, dp, H));
     else LF_TRY(edge_eval_kind<2>(ctx, W, rd2, scale, x->p, f != nullptr, gp, dp, H));
-    if (f) {
-        double s = 0.0;
-        LF_TRY(read_back(ctx, ctx->scal + 32, &s, 1));
-        *f = scale * (0.5 * s);
-    }
-    return 0;
+    return eval_finish(ctx, scale, f);
 }

@@ -149,7 +149,7 @@ struct PairRow {
 // Row form, two rows per lane.  WF: the energy goes to the reduction (every point edge is seen from both ends, at component 0 of either: the host
 // halves the sum); WV: grad / diag / hval, each optional.  <WF, !WV> writes nothing.  The slot loop is rolled for every kind, as the scalar kinds
 // 1 and 2 (FINDINGS.md 23 has the resource report).
-template <int DIM, int KIND, bool WF, bool WV>
+template <bool WF, bool WV, int DIM, int KIND>
 struct PairRowF {
     PairPot<KIND> pot;
     const int32_t* idx;
@@ -178,23 +178,13 @@ struct PairRowF {
             double h0 = 0.0, h1 = 0.0;
             const bool s0 = r0.slot(pot, x, scale, k, jj.x, ww.x, h0);
             const bool s1 = r1.slot(pot, x, scale, k, jj.y, ww.y, h1);
-            if (WV && hval) {
-                if (s0 && s1) st2(hval + i + o, make_double2(h0, h1));
-                else if (s0) hval[i + o] = h0;
-                else if (s1) hval[i + 1 + o] = h1;
-            }
+            if (WV && hval) store_rows(hval, i, o, s0, s1, h0, h1);
         }
         if (WF) red[0] += r0.e + r1.e;
         if (WV) {
             if (hval) { r0.intra(scale, hval, npad); r1.intra(scale, hval, npad); }
-            if (grad) {
-                if (r1.on) { const double2 s = ld2(grad + i); st2(grad + i, make_double2(fma(scale, r0.g, s.x), fma(scale, r1.g, s.y))); }
-                else grad[i] = fma(scale, r0.g, grad[i]);
-            }
-            if (diag) {
-                if (r1.on) { const double2 s = ld2(diag + i); st2(diag + i, make_double2(fma(scale, r0.d, s.x), fma(scale, r1.d, s.y))); }
-                else diag[i] = fma(scale, r0.d, diag[i]);
-            }
+            if (grad) add_rows(grad, i, r1.on, scale, r0.g, r1.g);
+            if (diag) add_rows(diag, i, r1.on, scale, r0.d, r1.d);
         }
     }
 };
@@ -255,9 +245,7 @@ struct PairOwnF {
             double h0 = 0.0, h1 = 0.0;
             const bool s0 = pair_own_slot<DIM, KIND>(pot, x, scale, ridx, hrow, npad, Kr, i, v0, nrows, jj.x, ww.x, h0);
             const bool s1 = pair_own_slot<DIM, KIND>(pot, x, scale, ridx, hrow, npad, Kr, i + 1, v1, nrows, jj.y, ww.y, h1);
-            if (s0 && s1) st2(hval + i + o, make_double2(h0, h1));
-            else if (s0) hval[i + o] = h0;
-            else if (s1) hval[i + 1 + o] = h1;
+            store_rows(hval, i, o, s0, s1, h0, h1);
         }
     }
 };
@@ -267,22 +255,10 @@ static int pair_eval_kind(lfpsqp_ctx* ctx, const lfpsqp_sphess* W, double delta,
                           double* diag, lfpsqp_sphess* H) {
     const PairPot<KIND> pot{delta, rd2};
     const int64_t nrows = (int64_t)DIM * W->pts.npoints;
-    const bool wv = grad || diag || H;
-    double* red = ctx->scal + 32;
-    if (wantf && !wv)
-        return run_vec<PairRowF<DIM, KIND, true, false>, 1, NoPost>(
-            ctx, W->n, PairRowF<DIM, KIND, true, false>{pot, W->ridx, W->rval, W->npad, W->Kr, nrows, x, scale, nullptr, nullptr, nullptr}, 0u, red, NoPost());
-    double* hr = H ? H->rval : nullptr;
-    if (wantf)
-        LF_TRY((run_vec<PairRowF<DIM, KIND, true, true>, 1, NoPost>(
-            ctx, W->n, PairRowF<DIM, KIND, true, true>{pot, W->ridx, W->rval, W->npad, W->Kr, nrows, x, scale, grad, diag, hr}, 0u, red, NoPost())));
-    else
-        LF_TRY((run_vec<PairRowF<DIM, KIND, false, true>, 0, NoPost>(
-            ctx, W->n, PairRowF<DIM, KIND, false, true>{pot, W->ridx, W->rval, W->npad, W->Kr, nrows, x, scale, grad, diag, hr}, 0u, nullptr, NoPost())));
-    if (H && W->Ke > 0)
-        LF_TRY((run_vec<PairOwnF<DIM, KIND>, 0, NoPost>(
-            ctx, W->n, PairOwnF<DIM, KIND>{pot, W->eidx, W->eval, W->npad, W->Ke, W->ridx, H->rval, W->Kr, nrows, x, scale, H->eval}, 0u, nullptr, NoPost())));
-    return 0;
+    return eval_launch<PairRowF, DIM, KIND>(
+        ctx, W, wantf, grad, diag, H,
+        PairOwnF<DIM, KIND>{pot, W->eidx, W->eval, W->npad, W->Ke, W->ridx, H ? H->rval : nullptr, W->Kr, nrows, x, scale, H ? H->eval : nullptr},
+        pot, W->ridx, W->rval, W->npad, W->Kr, nrows, x, scale);
 }
 
 template <int DIM>
@@ -302,24 +278,13 @@ extern "C" int lfpsqp_sphess_pair_eval(lfpsqp_ctx* ctx, const lfpsqp_sphess* W, 
     LF_ARG(ctx, ctx && W && x && kind >= 0 && kind <= 2 && std::isfinite(scale));
     LF_ARG(ctx, W->pts.dim == 2 || W->pts.dim == 3);             // a handle of lfpsqp_sphess_create_points (or a handle on its pattern)
     const int64_t nrows = (int64_t)W->pts.dim * W->pts.npoints;
-    LF_ARG(ctx, x->n >= nrows);
     LF_ARG(ctx, kind != 1 || (std::isfinite(delta) && delta >= 0.0));
     LF_ARG(ctx, kind != 2 || (std::isfinite(delta) && delta > 0.0));
-    LF_ARG(ctx, (!grad || (grad->n >= nrows && grad->p != x->p)) && (!diag || (diag->n >= nrows && diag->p != x->p)) && (!grad || !diag || grad->p != diag->p));
-    // H: another handle on W's pattern (W itself would lose the weights it is evaluated from)
-    LF_ARG(ctx, !H || (H != W && H->ridx == W->ridx && H->eidx == W->eidx && H->rval != W->rval));
-    if (ctx->comm_active())        // (a rank sees its own rows only: the edges across the shard boundaries would silently drop out)
-        return set_err(ctx, LFPSQP_ERR_UNSUPPORTED, "lfpsqp_sphess_pair_eval: one rank only (no halo exchange between row shards)");
-    if (f) *f = 0.0;
+    LF_TRY(eval_check(ctx, "lfpsqp_sphess_pair_eval", W, nrows, x, f, grad, diag, H));
     if (nrows == 0 || !(f || grad || diag || H)) return 0;
     const double rd2 = kind == 2 ? 1.0 / (delta * delta) : 0.0;
     double *gp = grad ? grad->p : nullptr, *dp = diag ? diag->p : nullptr;
     if (W->pts.dim == 2) LF_TRY(pair_eval_dim<2>(ctx, W, kind, delta, rd2, scale, x->p, f != nullptr, gp, dp, H));
     else LF_TRY(pair_eval_dim<3>(ctx, W, kind, delta, rd2, scale, x->p, f != nullptr, gp, dp, H));
-    if (f) {
-        double s = 0.0;
-        LF_TRY(read_back(ctx, ctx->scal + 32, &s, 1));
-        *f = scale * (0.5 * s);
-    }
-    return 0;
+    return eval_finish(ctx, scale, f);
 }

@@ -35,7 +35,7 @@ __device__ __forceinline__ double chain_sum(const double* vals, const int32_t* n
     return s;
 }
 
-// Row form, two rows per lane: per slot one int2 of source positions, the gather of vals, one 16-byte store into H's slot; then the diagonal, which
+// Either form, two rows per lane: per slot one int2 of source positions, the gather of vals, one 16-byte store into H's slot; then the diagonal, which
 // OVERWRITES.  hval == nullptr: the diagonal alone (K = 0); diag == nullptr: the slots alone.  The pad row behind an odd n holds -1 in every array
 // of the map: its value is computed (+0.0) and dropped, a single store goes to row n - 1.  DUP = false reads no `next` and has no inner loop.
 template <bool DUP>
@@ -57,38 +57,12 @@ struct ValRowF {
             const int64_t o = (int64_t)k * npad;
             const int2 pp = *reinterpret_cast<const int2*>(sp + o);
             const double h0 = chain_sum<DUP>(vals, next, pp.x), h1 = chain_sum<DUP>(vals, next, pp.y);
-            if (v1) st2(hval + i + o, make_double2(h0, h1));
-            else hval[i + o] = h0;
+            store_rows(hval, i, o, v1, h0, h1);
         }
         if (diag) {
             const int2 pp = *reinterpret_cast<const int2*>(dsrc + i);
             const double d0 = chain_sum<DUP>(vals, next, pp.x), d1 = chain_sum<DUP>(vals, next, pp.y);
-            if (v1) st2(diag + i, make_double2(d0, d1));
-            else diag[i] = d0;
-        }
-    }
-};
-
-// Edge form: the same per owner slot
-template <bool DUP>
-struct ValOwnF {
-    const int32_t* src;
-    const int32_t* next;
-    const double* vals;
-    int64_t npad;
-    int K;
-    double* hval;
-    __device__ __forceinline__ bool skip() const { return false; }
-    __device__ __forceinline__ void apply(int64_t i, bool v0, bool v1, double*) const {
-        if (!v0) return;
-        const int32_t* sp = src + i;
-#pragma unroll 4
-        for (int k = 0; k < K; ++k) {
-            const int64_t o = (int64_t)k * npad;
-            const int2 pp = *reinterpret_cast<const int2*>(sp + o);
-            const double h0 = chain_sum<DUP>(vals, next, pp.x), h1 = chain_sum<DUP>(vals, next, pp.y);
-            if (v1) st2(hval + i + o, make_double2(h0, h1));
-            else hval[i + o] = h0;
+            store_rows(diag, i, 0, v1, d0, d1);
         }
     }
 };
@@ -99,8 +73,9 @@ static int set_values_launch(lfpsqp_ctx* ctx, const lfpsqp_sphess_map* M, const 
     if (rows || diag)
         LF_TRY((run_vec<ValRowF<DUP>, 0, NoPost>(
             ctx, M->n, ValRowF<DUP>{M->rsrc, M->dsrc, M->next, vals, M->npad, rows ? M->Kr : 0, rows ? H->rval : nullptr, diag}, 0u, nullptr, NoPost())));
-    if (H && M->Ke > 0)
-        LF_TRY((run_vec<ValOwnF<DUP>, 0, NoPost>(ctx, M->n, ValOwnF<DUP>{M->esrc, M->next, vals, M->npad, M->Ke, H->eval}, 0u, nullptr, NoPost())));
+    if (H && M->Ke > 0)                                 // the edge form: the same per owner slot, no diagonal
+        LF_TRY((run_vec<ValRowF<DUP>, 0, NoPost>(ctx, M->n, ValRowF<DUP>{M->esrc, M->dsrc, M->next, vals, M->npad, M->Ke, H->eval, nullptr}, 0u, nullptr,
+                                                  NoPost())));
     return 0;
 }
 

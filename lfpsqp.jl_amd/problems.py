@@ -179,7 +179,50 @@ def difference_band(n: int, order: int, kappa: float = 1.0):
     return kappa * diag, kappa * off
 
 
-class ChainSeparableLinear(SeparableLinearBallBox):
+class _LaplacianSeparableLinear(SeparableLinearBallBox):
+    """What :class:`ChainSeparableLinear`, :class:`GridSeparableLinear` and :class:`GraphSeparableLinear` share: a separable objective plus a
+    quadratic term 1/2 x'(kappa L)x with a CONSTANT symmetric kappa L.  A subclass sets ``_deg`` (device, N entries: the diagonal of kappa L, zero
+    on the slack row) and its couplings, defines ``_operator(dg)`` -- kappa L as a coupled operator with the diagonal ``dg`` -- and ends its
+    constructor with ``_init_laplacian()``."""
+
+    def _init_laplacian(self):
+        self._lap = self._operator(self._deg)
+        self._tmp = self.ctx.vector(self.N)
+        self._lap2 = self._tmp2 = None                                    # the same over stacked iterates [x | gap | y] (bounds): zero on the y half
+
+    def _smooth(self, x: DeviceVector):
+        """tmp = kappa L x (x plain, or stacked: the x half)."""
+        if x.n == self.N:
+            return self._lap.mul_(self._tmp, x)
+        if self._lap2 is None:
+            from .inequality import StackedVector
+            deg2 = StackedVector(self.ctx, self.N)
+            deg2.copy_range_from(self._deg, self.N)
+            self._lap2 = self._operator(deg2)
+            self._tmp2 = StackedVector(self.ctx, self.N)
+        return self._lap2.mul_(self._tmp2, x)
+
+    def f(self, x: DeviceVector) -> float:
+        from .device import dot
+        return super().f(x) + 0.5 * dot(x, self._smooth(x))
+
+    def grad_(self, g: DeviceVector, x: DeviceVector):
+        from .device import axpby
+        super().grad_(g, x)
+        axpby(1.0, self._smooth(x), 1.0, g)
+
+    def diag_objective_(self, hx: DeviceVector, x: DeviceVector):
+        from .device import axpby
+        super().diag_objective_(hx, x)
+        axpby(1.0, self._deg, 1.0, hx)
+
+    def diag_(self, hx: DeviceVector, x: DeviceVector, lam: np.ndarray):
+        from .device import axpby
+        super().diag_(hx, x, lam)
+        axpby(1.0, self._deg, 1.0, hx)
+
+
+class ChainSeparableLinear(_LaplacianSeparableLinear):
     """A separable objective plus a CHAIN term: f(x) = sum_i phi(x_i - c_i; a_i) + kappa/2 ||D^r x||^2, D^r the r-th forward difference over the n
     user variables (``order`` r = 1 .. 4; r = 1: kappa/2 sum_{i<n-1} (x_{i+1} - x_i)^2, smoothing / first differences; r = 2: Whittaker /
     Hodrick-Prescott smoothing, curvature penalties -- the kind of objective whose Hessian the reference reaches only through hess_lag_vec!,
@@ -195,7 +238,6 @@ class ChainSeparableLinear(SeparableLinearBallBox):
         assert kw.get("n_global", n) in (None, n), "chain objective: one rank (the couplings would cross the shard boundaries)"
         assert int(order) in (1, 2, 3, 4), "chain objective: order 1 .. 4"
         super().__init__(ctx, n, m, Jct, b, kind, a, c, **kw)
-        from .projcg import BandedOperator, TridiagonalOperator
         self.kappa = float(kappa)
         self.order = int(order)
         N = self.N                                                        # n, or n + 1 with the ball's slack variable (no chain term on it)
@@ -207,50 +249,18 @@ class ChainSeparableLinear(SeparableLinearBallBox):
             off[n - 1:] = 0.0                                             # (entry n-1 would couple the last variable to the slack row; N-1 is ignored)
             self._deg = ctx.vector(N, deg)
             self.offdiag = ctx.vector(N, off)
-            self._lap = TridiagonalOperator(0.0, self._deg, self.offdiag)     # kappa * L, L = the path graph's Laplacian
         else:
             offs = np.zeros((N, self.order), order='F')
             deg[:n], offs[:n] = difference_band(n, self.order, self.kappa)   # (entries i + k >= n are zero: no coupling to the slack row)
             self._deg = ctx.vector(N, deg)
             self.offdiags = ctx.matrix(N, self.order, offs)
-            self._lap = BandedOperator(0.0, self._deg, self.offdiags, self.order)    # kappa D'D
-        self._tmp = ctx.vector(N)
-        self._lap2 = self._tmp2 = None                                    # the same over stacked iterates [x | gap | y] (bounds): zero on the y half
+        self._init_laplacian()
 
-    def _chain(self, x: DeviceVector):
-        """tmp = kappa D'D x (x plain, or stacked: the x half)."""
-        if x.n == self.N:
-            return self._lap.mul_(self._tmp, x)
-        if self._lap2 is None:
-            from .inequality import StackedVector
-            from .projcg import BandedOperator, TridiagonalOperator
-            deg2 = StackedVector(self.ctx, self.N)
-            deg2.copy_range_from(self._deg, self.N)
-            if self.order == 1:
-                self._lap2 = TridiagonalOperator(0.0, deg2, self.offdiag)
-            else:
-                self._lap2 = BandedOperator(0.0, deg2, self.offdiags, self.order)
-            self._tmp2 = StackedVector(self.ctx, self.N)
-        return self._lap2.mul_(self._tmp2, x)
-
-    def f(self, x: DeviceVector) -> float:
-        from .device import dot
-        return super().f(x) + 0.5 * dot(x, self._chain(x))
-
-    def grad_(self, g: DeviceVector, x: DeviceVector):
-        from .device import axpby
-        super().grad_(g, x)
-        axpby(1.0, self._chain(x), 1.0, g)
-
-    def diag_objective_(self, hx: DeviceVector, x: DeviceVector):
-        from .device import axpby
-        super().diag_objective_(hx, x)
-        axpby(1.0, self._deg, 1.0, hx)
-
-    def diag_(self, hx: DeviceVector, x: DeviceVector, lam: np.ndarray):
-        from .device import axpby
-        super().diag_(hx, x, lam)
-        axpby(1.0, self._deg, 1.0, hx)
+    def _operator(self, dg):
+        from .projcg import BandedOperator, TridiagonalOperator
+        if self.order == 1:
+            return TridiagonalOperator(0.0, dg, self.offdiag)            # kappa * L, L = the path graph's Laplacian
+        return BandedOperator(0.0, dg, self.offdiags, self.order)        # kappa D'D
 
 
 def graph_diagonals(n: int, i, j, w):
@@ -353,7 +363,7 @@ def grid_laplacian(shape, kappa: float = 1.0, periodic=False, corners: bool = Fa
     return diag, np.asfortranarray(np.stack(cols, axis=1)), tuple(dists)
 
 
-class GridSeparableLinear(SeparableLinearBallBox):
+class GridSeparableLinear(_LaplacianSeparableLinear):
     """A separable objective plus a GRID smoothness term: f(x) = sum_i phi(x_i - c_i; a_i) + kappa/2 sum_{grid edges (i,j)} (x_i - x_j)^2 over a
     2-D or 3-D field of ``shape`` in row-major order (an image, a volume: diffusion / Tikhonov smoothing) under dense linear equalities, with the
     optional ball (slack variable) and box bounds of :class:`QuadLinearBallBox`.  The Lagrangian Hessian is a diagonal, phi''(x_i) + kappa deg_i
@@ -369,7 +379,6 @@ class GridSeparableLinear(SeparableLinearBallBox):
         n = int(np.prod(shape))
         assert kw.get("n_global", n) in (None, n), "grid objective: one rank (the couplings would cross the shard boundaries)"
         super().__init__(ctx, n, m, Jct, b, kind, a, c, **kw)
-        from .projcg import DiagonalsOperator
         self.shape = tuple(int(s) for s in shape)
         self.kappa = float(kappa)
         N = self.N                                                        # n, or n + 1 with the ball's slack variable (no coupling to it)
@@ -379,44 +388,14 @@ class GridSeparableLinear(SeparableLinearBallBox):
         deg[:n], off[:n] = deg_h, off_h
         self._deg = ctx.vector(N, deg)
         self.diagonals = (dists, ctx.matrix(N, len(dists), off))
-        self._lap = DiagonalsOperator(0.0, self._deg, self.diagonals[1], dists)      # kappa L
-        self._tmp = ctx.vector(N)
-        self._lap2 = self._tmp2 = None                                    # the same over stacked iterates [x | gap | y] (bounds): zero on the y half
+        self._init_laplacian()
 
-    def _smooth(self, x: DeviceVector):
-        """tmp = kappa L x (x plain, or stacked: the x half)."""
-        if x.n == self.N:
-            return self._lap.mul_(self._tmp, x)
-        if self._lap2 is None:
-            from .inequality import StackedVector
-            from .projcg import DiagonalsOperator
-            deg2 = StackedVector(self.ctx, self.N)
-            deg2.copy_range_from(self._deg, self.N)
-            self._lap2 = DiagonalsOperator(0.0, deg2, self.diagonals[1], self.diagonals[0])
-            self._tmp2 = StackedVector(self.ctx, self.N)
-        return self._lap2.mul_(self._tmp2, x)
-
-    def f(self, x: DeviceVector) -> float:
-        from .device import dot
-        return super().f(x) + 0.5 * dot(x, self._smooth(x))
-
-    def grad_(self, g: DeviceVector, x: DeviceVector):
-        from .device import axpby
-        super().grad_(g, x)
-        axpby(1.0, self._smooth(x), 1.0, g)
-
-    def diag_objective_(self, hx: DeviceVector, x: DeviceVector):
-        from .device import axpby
-        super().diag_objective_(hx, x)
-        axpby(1.0, self._deg, 1.0, hx)
-
-    def diag_(self, hx: DeviceVector, x: DeviceVector, lam: np.ndarray):
-        from .device import axpby
-        super().diag_(hx, x, lam)
-        axpby(1.0, self._deg, 1.0, hx)
+    def _operator(self, dg):
+        from .projcg import DiagonalsOperator
+        return DiagonalsOperator(0.0, dg, self.diagonals[1], self.diagonals[0])      # kappa L
 
 
-class GraphSeparableLinear(SeparableLinearBallBox):
+class GraphSeparableLinear(_LaplacianSeparableLinear):
     """A separable objective plus a smoothness term on an arbitrary GRAPH: f(x) = sum_i phi(x_i - c_i; a_i) + kappa/2 sum_e w_e (x_i - x_j)^2 over
     the undirected edges ``edges = (i, j, w)`` (0-based index arrays, ``w`` a scalar or one weight per edge; repeated edges add up) -- a triangle
     mesh, a k-nearest-neighbour graph, a grid in any numbering, at most 32 neighbours per vertex -- under dense linear equalities, with the optional
@@ -430,54 +409,55 @@ class GraphSeparableLinear(SeparableLinearBallBox):
         assert kw.get("n_global", n) in (None, n), "graph objective: one rank (the couplings would cross the shard boundaries)"
         assert edges is not None and len(edges) == 3, "graph objective: edges = (i, j, w)"
         super().__init__(ctx, n, m, Jct, b, kind, a, c, **kw)
-        from .projcg import SparseHessian, SparseOperator
+        from .projcg import SparseHessian
         self.kappa = float(kappa)
         N = self.N                                                        # n, or n + 1 with the ball's slack variable (no coupling to it)
-        ei, ej = (np.asarray(e, dtype=np.int64).ravel() for e in edges[:2])
-        assert ei.shape == ej.shape and np.all((0 <= ei) & (ei < n) & (0 <= ej) & (ej < n)), "graph objective: edges between the n variables"
-        w = self.kappa * np.broadcast_to(np.asarray(edges[2], dtype=np.float64), ei.shape)
+        ei, ej, w = _edge_list(edges, n, "graph objective: edges between the n variables")
+        w = self.kappa * w
         deg = np.zeros(N)
         deg[:n] = np.bincount(ei, w, n) + np.bincount(ej, w, n)
         self._deg = ctx.vector(N, deg)
         self.sparse_hessian = SparseHessian(ctx, N, ei, ej, -w)
-        self._lap = SparseOperator(0.0, self._deg, self.sparse_hessian)    # kappa L
-        self._tmp = ctx.vector(N)
-        self._lap2 = self._tmp2 = None                                    # the same over stacked iterates [x | gap | y] (bounds): zero on the y half
+        self._init_laplacian()
 
-    def _smooth(self, x: DeviceVector):
-        """tmp = kappa L x (x plain, or stacked: the x half)."""
-        if x.n == self.N:
-            return self._lap.mul_(self._tmp, x)
-        if self._lap2 is None:
-            from .inequality import StackedVector
-            from .projcg import SparseOperator
-            deg2 = StackedVector(self.ctx, self.N)
-            deg2.copy_range_from(self._deg, self.N)
-            self._lap2 = SparseOperator(0.0, deg2, self.sparse_hessian)
-            self._tmp2 = StackedVector(self.ctx, self.N)
-        return self._lap2.mul_(self._tmp2, x)
+    def _operator(self, dg):
+        from .projcg import SparseOperator
+        return SparseOperator(0.0, dg, self.sparse_hessian)               # kappa L
+
+
+def _edge_list(edges, count: int, what: str):
+    """``edges = (i, j, w)`` as two int64 index arrays below ``count`` and one weight per edge (``w`` a scalar or an array)."""
+    ei, ej = (np.asarray(e, dtype=np.int64).ravel() for e in edges[:2])
+    assert ei.shape == ej.shape and np.all((0 <= ei) & (ei < count) & (0 <= ej) & (ej < count)), what
+    return ei, ej, np.broadcast_to(np.asarray(edges[2], dtype=np.float64), ei.shape)
+
+
+class _PotentialSeparableLinear(SeparableLinearBallBox):
+    """What :class:`GraphPotentialLinear` and :class:`PointPotentialLinear` share: a separable objective plus a term whose Hessian lives on a fixed
+    sparse pattern and changes with x.  A subclass builds ``weights`` (a :class:`SparseHessian`, never modified) and defines ``_term``: the
+    evaluator of ``weights`` with the term's parameters bound; ``sparse_hessian`` = ``weights.like()`` holds the current entries."""
+
+    def _init_potential(self, weights):
+        self.weights = weights
+        self.sparse_hessian = weights.like()
 
     def f(self, x: DeviceVector) -> float:
-        from .device import dot
-        return super().f(x) + 0.5 * dot(x, self._smooth(x))
+        return super().f(x) + self._term(x, want_f=True)
 
     def grad_(self, g: DeviceVector, x: DeviceVector):
-        from .device import axpby
         super().grad_(g, x)
-        axpby(1.0, self._smooth(x), 1.0, g)
+        self._term(x, grad=g)
 
     def diag_objective_(self, hx: DeviceVector, x: DeviceVector):
-        from .device import axpby
         super().diag_objective_(hx, x)
-        axpby(1.0, self._deg, 1.0, hx)
+        self._term(x, diag=hx, out=self.sparse_hessian)
 
     def diag_(self, hx: DeviceVector, x: DeviceVector, lam: np.ndarray):
-        from .device import axpby
         super().diag_(hx, x, lam)
-        axpby(1.0, self._deg, 1.0, hx)
+        self._term(x, diag=hx, out=self.sparse_hessian)
 
 
-class GraphPotentialLinear(SeparableLinearBallBox):
+class GraphPotentialLinear(_PotentialSeparableLinear):
     """A separable objective plus a NON-QUADRATIC edge term on a graph: f(x) = sum_i phi(x_i - c_i; a_i) + kappa sum_e w_e psi(x_i - x_j; delta) over
     the undirected edges ``edges = (i, j, w)`` of :class:`GraphSeparableLinear` -- ``edge_kind`` 0: psi = t^2/2 (that class's term), 1: t^2/2 +
     t^4/4 (stiffening), 2: the pseudo-Huber function delta^2 (sqrt(1 + (t/delta)^2) - 1) (edge-preserving smoothing) -- under the same constraint
@@ -498,32 +478,14 @@ class GraphPotentialLinear(SeparableLinearBallBox):
         super().__init__(ctx, n, m, Jct, b, kind, a, c, **kw)
         from .projcg import SparseHessian
         self.kappa, self.edge_kind, self.delta = float(kappa), int(edge_kind), float(delta)
-        ei, ej = (np.asarray(e, dtype=np.int64).ravel() for e in edges[:2])
-        assert ei.shape == ej.shape and np.all((0 <= ei) & (ei < n) & (0 <= ej) & (ej < n)), "graph objective: edges between the n variables"
-        w = np.broadcast_to(np.asarray(edges[2], dtype=np.float64), ei.shape)
-        self.weights = SparseHessian(ctx, self.N, ei, ej, w)             # N rows: the slack row, when the ball is there, has no edges
-        self.sparse_hessian = self.weights.like()
+        # N rows: the slack row, when the ball is there, has no edges
+        self._init_potential(SparseHessian(ctx, self.N, *_edge_list(edges, n, "graph objective: edges between the n variables")))
 
-    def _edge(self, x, grad=None, diag=None, out=None, want_f=False):
+    def _term(self, x, grad=None, diag=None, out=None, want_f=False):
         return self.weights.edge_eval(self.edge_kind, self.delta, self.kappa, x, grad, diag, out, want_f)
 
-    def f(self, x: DeviceVector) -> float:
-        return super().f(x) + self._edge(x, want_f=True)
 
-    def grad_(self, g: DeviceVector, x: DeviceVector):
-        super().grad_(g, x)
-        self._edge(x, grad=g)
-
-    def diag_objective_(self, hx: DeviceVector, x: DeviceVector):
-        super().diag_objective_(hx, x)
-        self._edge(x, diag=hx, out=self.sparse_hessian)
-
-    def diag_(self, hx: DeviceVector, x: DeviceVector, lam: np.ndarray):
-        super().diag_(hx, x, lam)
-        self._edge(x, diag=hx, out=self.sparse_hessian)
-
-
-class PointPotentialLinear(SeparableLinearBallBox):
+class PointPotentialLinear(_PotentialSeparableLinear):
     """A separable objective plus a PAIR potential between points of ``dim`` = 2 or 3 unknowns each: the n = dim*npoints variables are interleaved
     (x[dim*p + c] is component c of point p) and f(x) = sum_i phi(x_i - c_i; a_i) + kappa sum_e w_e psi(x_p - x_q; delta) over the undirected
     edges ``edges = (pi, pj, w)`` between POINTS -- ``pair_kind`` 0: psi = |t|^2/2, 1: (|t| - delta)^2/2 (a spring of rest length ``delta``: truss
@@ -547,29 +509,12 @@ class PointPotentialLinear(SeparableLinearBallBox):
         from .projcg import SparseHessian
         self.npoints, self.dim = int(npoints), int(dim)
         self.kappa, self.pair_kind, self.delta = float(kappa), int(pair_kind), float(delta)
-        ei, ej = (np.asarray(e, dtype=np.int64).ravel() for e in edges[:2])
-        assert ei.shape == ej.shape and np.all((0 <= ei) & (ei < npoints) & (0 <= ej) & (ej < npoints)), "point objective: edges between the points"
-        w = np.broadcast_to(np.asarray(edges[2], dtype=np.float64), ei.shape)
-        self.weights = SparseHessian.from_points(ctx, self.N, self.npoints, self.dim, ei, ej, w)   # N rows: the slack row, when the ball is there, has no edges
-        self.sparse_hessian = self.weights.like()
+        # N rows: the slack row, when the ball is there, has no edges
+        self._init_potential(SparseHessian.from_points(ctx, self.N, self.npoints, self.dim,
+                                                       *_edge_list(edges, npoints, "point objective: edges between the points")))
 
-    def _pair(self, x, grad=None, diag=None, out=None, want_f=False):
+    def _term(self, x, grad=None, diag=None, out=None, want_f=False):
         return self.weights.pair_eval(self.pair_kind, self.delta, self.kappa, x, grad, diag, out, want_f)
-
-    def f(self, x: DeviceVector) -> float:
-        return super().f(x) + self._pair(x, want_f=True)
-
-    def grad_(self, g: DeviceVector, x: DeviceVector):
-        super().grad_(g, x)
-        self._pair(x, grad=g)
-
-    def diag_objective_(self, hx: DeviceVector, x: DeviceVector):
-        super().diag_objective_(hx, x)
-        self._pair(x, diag=hx, out=self.sparse_hessian)
-
-    def diag_(self, hx: DeviceVector, x: DeviceVector, lam: np.ndarray):
-        super().diag_(hx, x, lam)
-        self._pair(x, diag=hx, out=self.sparse_hessian)
 
 
 class SeparableElementwiseBox(SeparableLinearBallBox):

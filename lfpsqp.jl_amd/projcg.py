@@ -204,6 +204,17 @@ class DiagonalsOperator(_CoupledOperator):
         return solve(*head, self.a0, self._dg_h(), self.off.h, len(self.dists), self._dist_c, *tail)
 
 
+def _triplets(who: str, names: str, i, j, w=None):
+    """The index lists of an edge / triplet list as contiguous int64 arrays of one length, with ``w`` (a scalar or one value per entry) as a
+    contiguous float64 array of that length."""
+    import numpy as np
+    ii = np.ascontiguousarray(np.asarray(i, dtype=np.int64).ravel())
+    jj = np.ascontiguousarray(np.asarray(j, dtype=np.int64).ravel())
+    if ii.shape != jj.shape:
+        raise ValueError(f"{who}: {names} of the same length")
+    return ii, jj, None if w is None else np.ascontiguousarray(np.broadcast_to(np.asarray(w, dtype=np.float64), ii.shape))
+
+
 class SparseHessian:
     """The symmetric off-diagonal part S of a sparse Hessian A = a0*I + diag(dg) + S as a device handle (lfpsqp_sphess): built ONCE from the
     undirected edge list ``(i, j, w)`` (0-based host arrays in any order, ``w`` a scalar or one value per edge: the entry A_ij = A_ji; duplicates
@@ -213,25 +224,20 @@ class SparseHessian:
     one-pass solve) describe what was built.  The diagonal is not part of it: i == j raises."""
 
     def __init__(self, ctx: Context, n: int, i, j, w):
-        import numpy as np
-        self.ctx = ctx
-        self.h = None
-        ii = np.ascontiguousarray(np.asarray(i, dtype=np.int64).ravel())
-        jj = np.ascontiguousarray(np.asarray(j, dtype=np.int64).ravel())
-        if ii.shape != jj.shape:
-            raise ValueError("SparseHessian: i and j of the same length")
-        ww = np.ascontiguousarray(np.broadcast_to(np.asarray(w, dtype=np.float64), ii.shape))
-        h = C.c_void_p()
-        ctx.check(ctx.L.lfpsqp_sphess_create(ctx.h, int(n), ii.size, ii.ctypes.data, jj.ctypes.data, ww.ctypes.data, C.byref(h)))
-        self.h = h
-        self._read_info()
+        ii, jj, ww = _triplets("SparseHessian", "i and j", i, j, w)
+        self._open(ctx, ctx.L.lfpsqp_sphess_create, int(n), ii.size, ii.ctypes.data, jj.ctypes.data, ww.ctypes.data)
 
-    def _read_info(self):
-        ctx = self.ctx
+    def _open(self, ctx, create, *args):
+        """This object as the wrapper of the handle that ``create(ctx.h, *args, &h)`` makes."""
+        self.ctx, self.h = ctx, None
+        h = C.c_void_p()
+        ctx.check(create(ctx.h, *args, C.byref(h)))
+        self.h = h
         out = [_capi.c_i64() for _ in range(6)]
         ctx.check(ctx.L.lfpsqp_sphess_info(self.h, *(C.byref(o) for o in out[:4])))
         ctx.check(ctx.L.lfpsqp_sphess_points_info(self.h, *(C.byref(o) for o in out[4:])))
         self.n, self.nedges, self.row_width, self.edge_width, self.npoints, self.dim = (o.value for o in out)
+        return self
 
     @classmethod
     def from_points(cls, ctx: Context, n: int, npoints: int, dim: int, pi, pj, w) -> "SparseHessian":
@@ -241,30 +247,25 @@ class SparseHessian:
         components holding 0.0.  ``n`` >= dim*npoints rows; the rows behind the points (a slack row) carry no couplings.  At most 15 neighbours
         per point in 2-D and 10 in 3-D (32 entries per scalar row).  ``npoints`` and ``dim`` are kept (0 for every other handle; :meth:`like`
         copies them); :meth:`pair_eval` evaluates the term."""
-        import numpy as np
-        ii = np.ascontiguousarray(np.asarray(pi, dtype=np.int64).ravel())
-        jj = np.ascontiguousarray(np.asarray(pj, dtype=np.int64).ravel())
-        if ii.shape != jj.shape:
-            raise ValueError("SparseHessian.from_points: pi and pj of the same length")
-        ww = np.ascontiguousarray(np.broadcast_to(np.asarray(w, dtype=np.float64), ii.shape))
-        h = C.c_void_p()
-        ctx.check(ctx.L.lfpsqp_sphess_create_points(ctx.h, int(n), int(npoints), int(dim), ii.size, ii.ctypes.data, jj.ctypes.data, ww.ctypes.data,
-                                                    C.byref(h)))
-        S = object.__new__(cls)
-        S.ctx, S.h = ctx, h
-        S._read_info()
-        return S
+        ii, jj, ww = _triplets("SparseHessian.from_points", "pi and pj", pi, pj, w)
+        return object.__new__(cls)._open(ctx, ctx.L.lfpsqp_sphess_create_points, int(n), int(npoints), int(dim), ii.size, ii.ctypes.data, jj.ctypes.data,
+                                         ww.ctypes.data)
 
     def like(self) -> "SparseHessian":
         """A second handle on the same pattern (lfpsqp_sphess_like): the index arrays are shared, the values are its own, initialised to this
         handle's.  The two may be closed in either order."""
+        return object.__new__(SparseHessian)._open(self.ctx, self.ctx.L.lfpsqp_sphess_like, self.h)
+
+    def _eval(self, entry: str, kind, delta, scale, x, grad, diag, out, want_f):
+        """lfpsqp_sphess_<entry>: what :meth:`edge_eval` and :meth:`pair_eval` document."""
         ctx = self.ctx
-        h = C.c_void_p()
-        ctx.check(ctx.L.lfpsqp_sphess_like(ctx.h, self.h, C.byref(h)))
-        H = object.__new__(SparseHessian)
-        H.ctx, H.h = ctx, h
-        H._read_info()
-        return H
+        if out is not None and out.ctx is not ctx:
+            raise ValueError(f"SparseHessian.{entry}: the output handle belongs to another context")
+        f = C.c_double()
+        ctx.check(getattr(ctx.L, "lfpsqp_sphess_" + entry)(ctx.h, self.h, int(kind), float(delta), float(scale), x.h, C.byref(f) if want_f else None,
+                                                           grad.h if grad is not None else None, diag.h if diag is not None else None,
+                                                           out.h if out is not None else None))
+        return f.value if want_f else None
 
     def edge_eval(self, kind: int, delta: float, scale: float, x, grad=None, diag=None, out=None, want_f: bool = True):
         """The edge term scale * sum_e w_e psi(x_i - x_j) with this handle's values as the weights w_e (lfpsqp_sphess_edge_eval; ``kind`` 0:
@@ -272,14 +273,7 @@ class SparseHessian:
         ADDS its gradient to ``grad`` and scale * sum_j w_ij psi'' to ``diag`` (the first ``n`` entries of either; ``x`` may be longer, a stacked
         iterate: its first ``n`` entries are read) and writes the off-diagonal values -(scale w_e) psi'' into ``out``, a handle made by
         :meth:`like`.  With nothing but the value asked for, the kernel writes no vector.  This handle is never modified."""
-        ctx = self.ctx
-        if out is not None and out.ctx is not ctx:
-            raise ValueError("SparseHessian.edge_eval: the output handle belongs to another context")
-        f = C.c_double()
-        ctx.check(ctx.L.lfpsqp_sphess_edge_eval(ctx.h, self.h, int(kind), float(delta), float(scale), x.h, C.byref(f) if want_f else None,
-                                                grad.h if grad is not None else None, diag.h if diag is not None else None,
-                                                out.h if out is not None else None))
-        return f.value if want_f else None
+        return self._eval("edge_eval", kind, delta, scale, x, grad, diag, out, want_f)
 
     def pair_eval(self, kind: int, delta: float, scale: float, x, grad=None, diag=None, out=None, want_f: bool = True):
         """The pair term scale * sum_e w_e psi(x_p - x_q) between the points of a handle made by :meth:`from_points`, with this handle's values as
@@ -289,14 +283,7 @@ class SparseHessian:
         dim*npoints entries; ``x`` may be longer), and ``out``, a handle made by :meth:`like`, receives the off-diagonal entries: the dim x dim
         block -(scale w)(a I + b t t') per edge and the entries between a point's own components.  This handle is never modified.  Kind 1 with
         two coincident points joined by an edge is a singularity of the potential: the outputs are then not finite."""
-        ctx = self.ctx
-        if out is not None and out.ctx is not ctx:
-            raise ValueError("SparseHessian.pair_eval: the output handle belongs to another context")
-        f = C.c_double()
-        ctx.check(ctx.L.lfpsqp_sphess_pair_eval(ctx.h, self.h, int(kind), float(delta), float(scale), x.h, C.byref(f) if want_f else None,
-                                                grad.h if grad is not None else None, diag.h if diag is not None else None,
-                                                out.h if out is not None else None))
-        return f.value if want_f else None
+        return self._eval("pair_eval", kind, delta, scale, x, grad, diag, out, want_f)
 
     @classmethod
     def from_pattern(cls, ctx: Context, n: int, rows, cols):
@@ -304,11 +291,7 @@ class SparseHessian:
         edge-list convention of the constructor; triplets with rows == cols are dropped for the handle) created with zero values, and
         ``pattern`` the :class:`SparsePattern` over the FULL triplet list, diagonal included, whose :meth:`SparsePattern.set_values` fills ``S`` (or
         any handle made by :meth:`like`) and a diagonal vector from ``nnz`` values."""
-        import numpy as np
-        rr = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).ravel())
-        cc = np.ascontiguousarray(np.asarray(cols, dtype=np.int64).ravel())
-        if rr.shape != cc.shape:
-            raise ValueError("SparseHessian.from_pattern: rows and cols of the same length")
+        rr, cc, _ = _triplets("SparseHessian.from_pattern", "rows and cols", rows, cols)
         off = rr != cc
         S = cls(ctx, n, rr[off], cc[off], 0.0)
         try:
@@ -340,14 +323,10 @@ class SparsePattern:
     on the pattern: it and the handles may be closed in any order."""
 
     def __init__(self, S: SparseHessian, rows, cols):
-        import numpy as np
         self.ctx = ctx = S.ctx
         self.h = None
         self._vals = None
-        rr = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).ravel())
-        cc = np.ascontiguousarray(np.asarray(cols, dtype=np.int64).ravel())
-        if rr.shape != cc.shape:
-            raise ValueError("SparsePattern: rows and cols of the same length")
+        rr, cc, _ = _triplets("SparsePattern", "rows and cols", rows, cols)
         h = C.c_void_p()
         ctx.check(ctx.L.lfpsqp_sphess_map_create(ctx.h, S.h, rr.size, rr.ctypes.data, cc.ctypes.data, C.byref(h)))
         self.h = h
