@@ -639,6 +639,53 @@ int lfpsqp_sphess_points_info(const lfpsqp_sphess* S, int64_t* npoints, int64_t*
 int lfpsqp_sphess_pair_eval(lfpsqp_ctx* ctx, const lfpsqp_sphess* W, int kind, double delta, double scale, const lfpsqp_vec* x, double* f,
                             lfpsqp_vec* grad, lfpsqp_vec* diag, lfpsqp_sphess* H);
 
+/* A PARAMETER PER EDGE AND FIXED POINTS: a truss has one natural length per bar and supports, sensor localisation one measured distance per pair
+ * and beacons at known positions:  scale * ( sum_e w_e psi(x_p - x_q; par_e) + sum_k u_k psi(x_{p_k} - a_k; par_k) ).  Both terms live on the
+ * pattern of lfpsqp_sphess_create_points -- an anchor contributes to its point's diagonal and to the entries between its own components only.
+ * lfpsqp_sphess_points_values: *out = a handle on W's PATTERN (shared index arrays, the reference count of lfpsqp_sphess_like; freed with
+ * lfpsqp_sphess_free) whose entries between two points hold vals[e] for the point edge e (all dim^2 of them, in both forms) and 0.0 inside a
+ * point.  W is a handle of lfpsqp_sphess_create_points or a handle on its pattern; lfpsqp_sphess_points_info reports for the result what it
+ * reports for W.  (pi, pj) must name exactly the distinct point edges of W, in any order and either orientation, each ONCE: a parameter does not
+ * add up.  LFPSQP_ERR_ARG, with the entry named in lfpsqp_last_error: an index outside [0, npoints), an edge that W does not have, a duplicate
+ * (mirrored included), a value that is not finite or negative; and, with the number of them: edges of W left without a value; W not a handle of
+ * points.  W's index arrays are read back from the device for the check.
+ * lfpsqp_anchors_create: nanchors fixed points; anchor k ties point[k] of W to the position pos[dim*k .. dim*k + dim - 1] with the weight u[k] and
+ * the parameter par[k] (par == NULL: every anchor uses the delta of the call).  W fixes (n, npoints, dim) and the padded length of the arrays; the
+ * object keeps these numbers and holds NO reference on W.  Stored in ELL form by scalar row, `width` slots (the most anchors on one point: what is
+ * present, at most LFPSQP_ANCHORS_MAX_POINT) of 24 bytes per row each: row dim*p + c of slot k holds component c of the position of the k-th anchor
+ * of point p, in the order of the list, and copies of its weight and parameter; an empty slot has the weight 0.0 and is skipped before position
+ * and parameter are loaded -- as an anchor with u = 0, which contributes nothing.  LFPSQP_ERR_ARG: a point outside [0, npoints); a pos, u or par
+ * that is not finite; a negative par; W not a handle of points.  LFPSQP_ERR_UNSUPPORTED: more than LFPSQP_ANCHORS_MAX_POINT anchors on one point
+ * (the count and the limit are in lfpsqp_last_error; a sensor hears a few beacons, a truss node has one support).
+ * lfpsqp_anchors_info: nanchors as given and width; either output may be NULL.
+ * lfpsqp_sphess_pair_eval_ex: lfpsqp_sphess_pair_eval -- its kinds, its outputs, its conventions: W is never written, H is a handle made by
+ * lfpsqp_sphess_like, any of f, grad, diag and H may be NULL, grad and diag are ADDED to and untouched behind dim*npoints, only the first
+ * dim*npoints entries of x are read -- with
+ *     P (or NULL): a handle on W's pattern, not H, whose entry at a neighbour's component-0 slot is that edge's parameter: l_e for kind 1, delta_e
+ *         for kind 2 (1/delta_e^2 is formed on the device as 1.0 / (delta_e delta_e), the host's expression in lfpsqp_sphess_pair_eval).  P == NULL:
+ *         every edge uses delta.  Kind 0 has no parameter and refuses a P;
+ *     A (or NULL): anchors made for W's (n, npoints, dim).  Per anchor t = x_p - a_k, q = |t|^2 and (psi, a, b) exactly as for a neighbour:
+ *         *f += scale u_k psi,  grad_(p,c) += scale u_k a t_c,  diag_(p,c) += scale u_k (a + b t_c^2),  H at ((p,c),(p,c')) += scale u_k b t_c t_c'
+ *         -- the anchors of a point follow its neighbours in the row's fma chains, in the order of the list; no entry between points changes.  With
+ *         kind 0 an anchor is the quadratic pin u |x_p - a|^2 / 2.
+ * With P == NULL and A == NULL the call IS lfpsqp_sphess_pair_eval.  A parameter held constant over the edges gives the bits of the uniform call;
+ * an anchor gives the bits of an edge of weight u_k to a frozen point that is the last neighbour of its point.  The signs of the per-edge values
+ * were checked at creation; delta_e == 0 under kind 2 is the caller's to avoid, as coincident points (an anchor on its point included) are under
+ * kind 1: the outputs are then NOT FINITE.
+ * LFPSQP_ERR_ARG: as for lfpsqp_sphess_pair_eval, the rules on delta applying where delta is used (P == NULL, or A given without par); P on
+ * another pattern, P == H, P with kind 0; A made for a handle of other (n, npoints, dim).  LFPSQP_ERR_UNSUPPORTED: a communicator. */
+int lfpsqp_sphess_points_values(lfpsqp_ctx* ctx, const lfpsqp_sphess* W, int64_t nedges, const int64_t* pi, const int64_t* pj, const double* vals,
+                                lfpsqp_sphess** out);
+typedef struct lfpsqp_anchors lfpsqp_anchors;
+#define LFPSQP_ANCHORS_MAX_POINT 8
+int lfpsqp_anchors_create(lfpsqp_ctx* ctx, const lfpsqp_sphess* W, int64_t nanchors, const int64_t* point, const double* pos /* nanchors x dim, row-major */,
+                          const double* u, const double* par /* or NULL */, lfpsqp_anchors** out);
+int lfpsqp_anchors_free(lfpsqp_ctx* ctx, lfpsqp_anchors* A);
+int lfpsqp_anchors_info(const lfpsqp_anchors* A, int64_t* nanchors, int64_t* width /* most anchors on one point */);
+int lfpsqp_sphess_pair_eval_ex(lfpsqp_ctx* ctx, const lfpsqp_sphess* W, int kind, double delta, const lfpsqp_sphess* P /* or NULL */,
+                               const lfpsqp_anchors* A /* or NULL */, double scale, const lfpsqp_vec* x, double* f, lfpsqp_vec* grad, lfpsqp_vec* diag,
+                               lfpsqp_sphess* H);
+
 /* VALUES SUPPLIED BY THE CALLER on a fixed pattern: the structure / values contract of a sparse NLP interface (declare the Hessian's structure
  * once, fill an array of values per iteration) for a Lagrangian Hessian that lfpsqp_sphess_edge_eval cannot express.
  * lfpsqp_sphess_map_create: built ONCE on the host from nnz triplet positions (rows, cols) (0-based, any order) against the pattern of S, and

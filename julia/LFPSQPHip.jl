@@ -262,6 +262,11 @@ c_sphess_edge_eval(ctx, W, kind, delta, scale, x, f, grad, diag, H) = ccall((:lf
 c_sphess_create_points(ctx, n, npoints, dim, nedges, pi, pj, w, out) = ccall((:lfpsqp_sphess_create_points, lib), Cint, (Ptr{Cvoid}, Int64, Int64, Cint, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ref{Ptr{Cvoid}}), ctx, n, npoints, dim, nedges, pi, pj, w, out)
 c_sphess_points_info(S, npoints, dim) = ccall((:lfpsqp_sphess_points_info, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), S, npoints, dim)
 c_sphess_pair_eval(ctx, W, kind, delta, scale, x, f, grad, diag, H) = ccall((:lfpsqp_sphess_pair_eval, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Float64, Float64, Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), ctx, W, kind, delta, scale, x, f, grad, diag, H)
+c_sphess_points_values(ctx, W, nedges, pi, pj, vals, out) = ccall((:lfpsqp_sphess_points_values, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ref{Ptr{Cvoid}}), ctx, W, nedges, pi, pj, vals, out)
+c_anchors_create(ctx, W, nanchors, point, pos, u, par, out) = ccall((:lfpsqp_anchors_create, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Ptr{Cvoid}}), ctx, W, nanchors, point, pos, u, par, out)
+c_anchors_free(ctx, A) = ccall((:lfpsqp_anchors_free, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), ctx, A)
+c_anchors_info(A, nanchors, width) = ccall((:lfpsqp_anchors_info, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), A, nanchors, width)
+c_sphess_pair_eval_ex(ctx, W, kind, delta, P, A, scale, x, f, grad, diag, H) = ccall((:lfpsqp_sphess_pair_eval_ex, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), ctx, W, kind, delta, P, A, scale, x, f, grad, diag, H)
 c_projcg_sparse(ctx, x, lam, a0, dg, S, Av, U, b, c, tol, maxit, nglob, flags, work, iters, nr) = ccall((:lfpsqp_projcg_sparse, lib), Cint,
     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{CBasis}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Int64, Int64, Cint, Ref{CWork}, Ref{Int64}, Ref{Float64}),
     ctx, x, lam, a0, dg, S, Av, U, b, c, tol, maxit, nglob, flags, work, iters, nr)
@@ -713,11 +718,51 @@ end
 # The pair term scale Σ_e w_e ψ(x_p - x_q) between points (lfpsqp_sphess_pair_eval; kind 0: |t|²/2, 1: a spring of rest length delta, 2: the radial
 # pseudo-Huber function with scale delta), with the conventions of edge_eval!: the value is returned, `grad` and `diag` are added to, `out` (a handle
 # made by `like`) receives the Hessian's entries, W is never modified.
-function pair_eval!(W::SparseHessian, kind::Integer, delta::Float64, scale::Float64, x::DeviceVector; grad=nothing, diag=nothing, out=nothing, want_f::Bool=true)
+# `params` (a handle made by point_values): one rest length (kind 1) or delta (kind 2) per edge instead of `delta`; `anchors` (a PointAnchors made for
+# W): scale Σ_k u_k ψ(x_p - a_k; par_k) on top.  With either the call is lfpsqp_sphess_pair_eval_ex.
+function pair_eval!(W::SparseHessian, kind::Integer, delta::Float64, scale::Float64, x::DeviceVector; grad=nothing, diag=nothing, out=nothing, want_f::Bool=true,
+                    params=nothing, anchors=nothing)
     f = Ref{Float64}(0.0)
-    check(W.ctx, c_sphess_pair_eval(W.ctx.h, W.h, Cint(kind), delta, scale, x.h, want_f ? f : Ptr{Float64}(C_NULL),
-                                    grad === nothing ? C_NULL : grad.h, diag === nothing ? C_NULL : diag.h, out === nothing ? C_NULL : out.h))
+    fp = want_f ? f : Ptr{Float64}(C_NULL)
+    gh = grad === nothing ? C_NULL : grad.h
+    dh = diag === nothing ? C_NULL : diag.h
+    oh = out === nothing ? C_NULL : out.h
+    if params === nothing && anchors === nothing
+        check(W.ctx, c_sphess_pair_eval(W.ctx.h, W.h, Cint(kind), delta, scale, x.h, fp, gh, dh, oh))
+    else
+        check(W.ctx, c_sphess_pair_eval_ex(W.ctx.h, W.h, Cint(kind), delta, params === nothing ? C_NULL : params.h, anchors === nothing ? C_NULL : anchors.h,
+                                           scale, x.h, fp, gh, dh, oh))
+    end
     return want_f ? f[] : nothing
+end
+# One PARAMETER per point edge of W as a handle on W's pattern (lfpsqp_sphess_points_values): V[e] on all dim² entries of the 1-based point edge
+# (I[e], J[e]), 0.0 inside a point.  The list names every point edge of W exactly once (a parameter does not add up).
+function point_values(W::SparseHessian, I::Vector{Int}, J::Vector{Int}, V::Vector{Float64})
+    length(I) == length(J) == length(V) || error("I, J and V are of different lengths")
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    check(W.ctx, c_sphess_points_values(W.ctx.h, W.h, Int64(length(V)), Int64.(I .- 1), Int64.(J .- 1), V, r))
+    P = SparseHessian(W.ctx, r[], W.n, W.nedges, W.row_width, W.edge_width)
+    finalizer(x -> c_sphess_free(x.ctx.h, x.h), P)
+    return P
+end
+# Fixed points (lfpsqp_anchors): anchor k ties the 1-based point `point[k]` of W to the position pos[:, k] (dim x nanchors, column-major: the C
+# side's nanchors x dim row-major) with the weight u[k] and the parameter par[k] (nothing: the delta of the call).  At most 8 on one point.
+mutable struct PointAnchors
+    ctx::HipContext
+    h::Ptr{Cvoid}
+    nanchors::Int
+    width::Int
+end
+function PointAnchors(W::SparseHessian, point::Vector{Int}, pos::Matrix{Float64}, u::Vector{Float64}, par::Union{Nothing,Vector{Float64}}=nothing)
+    size(pos, 2) == length(point) == length(u) || error("point, u and the columns of pos are of different lengths")
+    par === nothing || length(par) == length(u) || error("par and u are of different lengths")
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    check(W.ctx, c_anchors_create(W.ctx.h, W.h, Int64(length(u)), Int64.(point .- 1), pos, u, par === nothing ? Ptr{Float64}(C_NULL) : par, r))
+    na = Ref{Int64}(0); wd = Ref{Int64}(0)
+    check(W.ctx, c_anchors_info(r[], na, wd))
+    A = PointAnchors(W.ctx, r[], Int(na[]), Int(wd[]))
+    finalizer(x -> c_anchors_free(x.ctx.h, x.h), A)
+    return A
 end
 # The structure / values interface (lfpsqp_sphess_map): 1-based triplet positions (I[p], J[p]) declared ONCE against the pattern of S -- the
 # convention of SparseHessian (a triplet counts for A_ij and A_ji, duplicates and mirrored duplicates add up in the order given), and I[p] == J[p]
@@ -2246,7 +2291,7 @@ optimize(ctx::HipContext, f, grad!, c!, jac_c!, d!, jac_d!, hess_lag_vec!, x0::V
 
 export HipContext, HipError, DeviceOptions, DeviceVector, StackedVector, DeviceMatrix, SparseMatrix, spmv_t!, spmv_n!, to_dense!, DeviceBasis, DiagOperator, LowRankOperator, InequalityData, InequalityDecomp,
        InequalityDecompProject, ProjCGWork, DeviceConstraints, NR, ProjPenalty, ProjPenaltyWork, Euclidean, YRetract, ArmijoWork,
-       ExactLinesearchWork, LFPSQPParams, TerminationInfo, QuadLinearBallBox, SeparableLinearBallBox, ChainSeparableLinear, GraphPotentialLinear, like, edge_eval!, SparseHessianPoints, points_info, pair_eval!, SparsePattern, set_values!, TridiagonalOperator, BandedOperator, DiagonalsOperator, SparseHessian, SparseOperator, SeparableElementwiseBox, ElementwiseConstraints,
+       ExactLinesearchWork, LFPSQPParams, TerminationInfo, QuadLinearBallBox, SeparableLinearBallBox, ChainSeparableLinear, GraphPotentialLinear, like, edge_eval!, SparseHessianPoints, points_info, pair_eval!, point_values, PointAnchors, SparsePattern, set_values!, TridiagonalOperator, BandedOperator, DiagonalsOperator, SparseHessian, SparseOperator, SeparableElementwiseBox, ElementwiseConstraints,
        sin_system_constraints, sphere_system_constraints, clone, rowscale!, set_placement!, basis_and_vectors_placed, vectors_placed, placement_info, upload!, download, upload2!, download2, projcg!, retract!,
        retract_nr_batch!, pcg!, ProjPrecondition, ksvd!, armijo!, exact_linesearch!, optimize, optimize_core, hess_diag!, jac!, comm_unique_id, comm_init!, comm_p2p_export, comm_init_p2p!,
        shard_range, sync

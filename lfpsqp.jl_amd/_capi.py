@@ -191,6 +191,11 @@ _SIGS = {
     "lfpsqp_sphess_create_points": [P, c_i64, c_i64, C.c_int, c_i64, P, P, P, C.POINTER(P)],
     "lfpsqp_sphess_points_info": [P, C.POINTER(c_i64), C.POINTER(c_i64)],
     "lfpsqp_sphess_pair_eval": [P, P, C.c_int, c_dbl, c_dbl, P, PD, P, P, P],
+    "lfpsqp_sphess_points_values": [P, P, c_i64, P, P, P, C.POINTER(P)],
+    "lfpsqp_anchors_create": [P, P, c_i64, P, P, P, P, C.POINTER(P)],
+    "lfpsqp_anchors_free": [P, P],
+    "lfpsqp_anchors_info": [P, C.POINTER(c_i64), C.POINTER(c_i64)],
+    "lfpsqp_sphess_pair_eval_ex": [P, P, C.c_int, c_dbl, P, P, c_dbl, P, PD, P, P, P],
     "lfpsqp_sphess_map_create": [P, P, c_i64, P, P, C.POINTER(P)],
     "lfpsqp_sphess_map_free": [P, P],
     "lfpsqp_sphess_map_info": [P, C.POINTER(c_i64), C.POINTER(c_i64), C.POINTER(c_i64)],

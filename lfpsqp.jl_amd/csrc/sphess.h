@@ -21,6 +21,20 @@ struct lfpsqp_sphess {
     struct Points { int64_t npoints = 0; int dim = 0; } pts;
 };
 
+// Fixed points a_k that points of a handle of lfpsqp_sphess_create_points are tied to (lfpsqp_anchors_create), in ELL form BY SCALAR ROW as the
+// handle itself: `width` slots (the most anchors on one point) of npad entries.  Row dim*p + c of slot k holds component c of the position of the
+// k-th anchor of point p (in the order of the list) and copies of that anchor's weight and parameter; an empty slot (and every row behind the
+// points) holds 0.0 in all three.  The object keeps the four numbers of the handle it was made for and no reference on it.
+struct lfpsqp_anchors {
+    int64_t n = 0, npoints = 0, npad = 0;
+    int dim = 0;
+    int64_t nanchors = 0;
+    int width = 0;
+    double* pos = nullptr;          // [max(width, 1)][npad]
+    double* u = nullptr;
+    double* par = nullptr;          // nullptr: created without parameters (every anchor uses the call's delta)
+};
+
 namespace lfpsqp {
 
 // The row form as a kernel argument, with the interface of DiagsD (projcg.hip): the operator over vectors of n rows, couplings on the first nc.

@@ -186,6 +186,136 @@ int lfpsqp_sphess_like(lfpsqp_ctx* ctx, const lfpsqp_sphess* W, lfpsqp_sphess** 
     return 0;
 }
 
+// One value per point edge of W as a handle on W's pattern: a PARAMETER (a rest length), so nothing adds up -- the list must name every point edge
+// of W exactly once.  The list is checked against W's row form read back from the device; the value arrays are then those of a temporary handle
+// built from the same list (the builder is deterministic in the edge set, so its layout is W's: compared, index by index), copied into a _like
+// handle of W.
+int lfpsqp_sphess_points_values(lfpsqp_ctx* ctx, const lfpsqp_sphess* W, int64_t nedges, const int64_t* pi, const int64_t* pj, const double* vals,
+                                lfpsqp_sphess** out) {
+    LF_ARG(ctx, ctx && W && out && nedges >= 0 && (nedges == 0 || (pi && pj && vals)));
+    *out = nullptr;
+    LF_ARG(ctx, W->pts.dim == 2 || W->pts.dim == 3);             // a handle of lfpsqp_sphess_create_points (or a handle on its pattern)
+    const int dim = W->pts.dim;
+    const int64_t npoints = W->pts.npoints;
+    const size_t npad = (size_t)W->npad, rsz = (size_t)std::max(W->Kr, 1) * npad, esz = (size_t)std::max(W->Ke, 1) * npad;
+    std::vector<int32_t> ri(rsz), ei(esz);
+    LF_HIP(ctx, hipMemcpyAsync(ri.data(), W->ridx, rsz * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    LF_HIP(ctx, hipMemcpyAsync(ei.data(), W->eidx, esz * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    // q is a neighbour of p: component 0 of q sits in row dim*p
+    auto joined = [&](int64_t p, int64_t q) {
+        for (int k = 0; k < W->Kr; ++k)
+            if (ri[(size_t)k * npad + (size_t)(dim * p)] == (int32_t)(dim * q)) return true;
+        return false;
+    };
+    struct Named { int64_t p, q, e; };
+    std::vector<Named> pe((size_t)nedges);
+    for (int64_t e = 0; e < nedges; ++e) {
+        const int64_t p = pi[e], q = pj[e];
+        if (p < 0 || p >= npoints || q < 0 || q >= npoints) return set_err(ctx, LFPSQP_ERR_ARG, "sphess: point edge %lld out of range", (long long)e);
+        if (!std::isfinite(vals[e]) || vals[e] < 0.0) return set_err(ctx, LFPSQP_ERR_ARG, "sphess: the value of point edge %lld is not finite or negative", (long long)e);
+        if (p == q || !joined(p, q)) return set_err(ctx, LFPSQP_ERR_ARG, "sphess: point edge %lld is no edge of the handle", (long long)e);
+        pe[(size_t)e] = Named{std::min(p, q), std::max(p, q), e};
+    }
+    std::sort(pe.begin(), pe.end(), [](const Named& a, const Named& b) { return a.p != b.p ? a.p < b.p : a.q != b.q ? a.q < b.q : a.e < b.e; });
+    for (size_t k = 1; k < pe.size(); ++k)
+        if (pe[k].p == pe[k - 1].p && pe[k].q == pe[k - 1].q)
+            return set_err(ctx, LFPSQP_ERR_ARG, "sphess: point edge %lld repeats point edge %lld (a parameter does not add up)", (long long)pe[k].e,
+                           (long long)pe[k - 1].e);
+    const int64_t have = (W->nedges - npoints * (dim * (dim - 1) / 2)) / (dim * dim);
+    if (nedges != have)
+        return set_err(ctx, LFPSQP_ERR_ARG, "sphess: %lld of the handle's %lld point edges are missing a value", (long long)(have - nedges), (long long)have);
+    lfpsqp_sphess* T = nullptr;
+    LF_TRY(lfpsqp_sphess_create_points(ctx, W->n, npoints, dim, nedges, pi, pj, vals, &T));
+    bool same = T->Kr == W->Kr && T->Ke == W->Ke && T->npad == W->npad && T->nedges == W->nedges;
+    if (same) {
+        std::vector<int32_t> tr(rsz), te(esz);
+        same = hipMemcpyAsync(tr.data(), T->ridx, rsz * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
+               hipMemcpyAsync(te.data(), T->eidx, esz * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
+               hipStreamSynchronize(ctx->stream) == hipSuccess && tr == ri && te == ei;
+    }
+    lfpsqp_sphess* P = nullptr;
+    int rc = same ? lfpsqp_sphess_like(ctx, W, &P) : set_err(ctx, LFPSQP_ERR_ARG, "sphess: the point edges do not give the handle's layout");
+    if (rc == 0) {
+        const bool ok = hipMemcpyAsync(P->rval, T->rval, rsz * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream) == hipSuccess &&
+                        hipMemcpyAsync(P->eval, T->eval, esz * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream) == hipSuccess &&
+                        hipStreamSynchronize(ctx->stream) == hipSuccess;
+        if (!ok) {
+            lfpsqp_sphess_free(ctx, P);
+            rc = set_err(ctx, LFPSQP_ERR_HIP, "sphess: device copy failed");
+        }
+    }
+    lfpsqp_sphess_free(ctx, T);
+    if (rc == 0) *out = P;
+    return rc;
+}
+
+int lfpsqp_anchors_create(lfpsqp_ctx* ctx, const lfpsqp_sphess* W, int64_t nanchors, const int64_t* point, const double* pos, const double* u,
+                          const double* par, lfpsqp_anchors** out) {
+    LF_ARG(ctx, ctx && W && out && nanchors >= 0 && (nanchors == 0 || (point && pos && u)));
+    *out = nullptr;
+    LF_ARG(ctx, W->pts.dim == 2 || W->pts.dim == 3);             // a handle of lfpsqp_sphess_create_points (or a handle on its pattern)
+    const int dim = W->pts.dim;
+    const int64_t npoints = W->pts.npoints;
+    std::vector<int32_t> cnt((size_t)std::max<int64_t>(npoints, 1), 0);
+    int width = 0;
+    for (int64_t k = 0; k < nanchors; ++k) {
+        if (point[k] < 0 || point[k] >= npoints) return set_err(ctx, LFPSQP_ERR_ARG, "anchors: the point of anchor %lld is out of range", (long long)k);
+        bool fin = std::isfinite(u[k]) && (!par || std::isfinite(par[k]));
+        for (int c = 0; c < dim; ++c) fin = fin && std::isfinite(pos[dim * k + c]);
+        if (!fin) return set_err(ctx, LFPSQP_ERR_ARG, "anchors: anchor %lld has a position, a weight or a parameter that is not finite", (long long)k);
+        if (par && par[k] < 0.0) return set_err(ctx, LFPSQP_ERR_ARG, "anchors: the parameter of anchor %lld is negative", (long long)k);
+        width = std::max(width, ++cnt[(size_t)point[k]]);
+    }
+    if (width > LFPSQP_ANCHORS_MAX_POINT)
+        return set_err(ctx, LFPSQP_ERR_UNSUPPORTED, "anchors: a point with %d anchors (> %d)", width, LFPSQP_ANCHORS_MAX_POINT);
+    const size_t npad = (size_t)W->npad, sz = (size_t)std::max(width, 1) * npad;
+    std::vector<double> hp(sz, 0.0), hu(sz, 0.0), hr(par ? sz : 0, 0.0);
+    std::fill(cnt.begin(), cnt.end(), 0);
+    for (int64_t k = 0; k < nanchors; ++k) {
+        const size_t s = (size_t)cnt[(size_t)point[k]]++ * npad + (size_t)(dim * point[k]);
+        for (int c = 0; c < dim; ++c) {
+            hp[s + (size_t)c] = pos[dim * k + c];
+            hu[s + (size_t)c] = u[k];
+            if (par) hr[s + (size_t)c] = par[k];
+        }
+    }
+    lfpsqp_anchors* A = new lfpsqp_anchors();
+    A->n = W->n; A->npoints = npoints; A->npad = W->npad; A->dim = dim; A->nanchors = nanchors; A->width = width;
+    bool ok = true;
+    auto dev_copy = [&](double** dst, const std::vector<double>& src) {
+        if (!ok) return;
+        ok = hipMalloc((void**)dst, src.size() * sizeof(double)) == hipSuccess;
+        if (ok) ok = hipMemcpyAsync(*dst, src.data(), src.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
+    };
+    dev_copy(&A->pos, hp);
+    dev_copy(&A->u, hu);
+    if (par) dev_copy(&A->par, hr);
+    if (ok) ok = hipStreamSynchronize(ctx->stream) == hipSuccess;
+    if (!ok) {
+        lfpsqp_anchors_free(ctx, A);
+        return set_err(ctx, LFPSQP_ERR_HIP, "anchors: device allocation / upload failed");
+    }
+    *out = A;
+    return 0;
+}
+
+int lfpsqp_anchors_free(lfpsqp_ctx* ctx, lfpsqp_anchors* A) {
+    if (!A) return 0;
+    if (ctx) (void)hipStreamSynchronize(ctx->stream);
+    for (void* p : {(void*)A->pos, (void*)A->u, (void*)A->par})
+        if (p) (void)hipFree(p);
+    delete A;
+    return 0;
+}
+
+int lfpsqp_anchors_info(const lfpsqp_anchors* A, int64_t* nanchors, int64_t* width) {
+    if (!A) return LFPSQP_ERR_ARG;
+    if (nanchors) *nanchors = A->nanchors;
+    if (width) *width = A->width;
+    return 0;
+}
+
 int lfpsqp_sphess_info(const lfpsqp_sphess* S, int64_t* n, int64_t* nedges, int64_t* row_width, int64_t* edge_width) {
     if (!S) return LFPSQP_ERR_ARG;
     if (n) *n = S->n;

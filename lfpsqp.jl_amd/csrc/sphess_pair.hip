@@ -32,6 +32,9 @@
 //   a stored cross-point value: fl(scale w) and the product: cv + 2.  grad term a t_c: count(a) + 2.
 //   a row sum (grad, diag, an intra-point entry): at most deg additions of the fma chain (one per neighbour) and one rounding with scale:
 //           deg + count(a) + 3 (grad), deg + cv + 1 (diag, intra-point).   f: as in sphess_edge.hip, npoints deg + count(psi) + 1.
+//   lfpsqp_sphess_pair_eval_ex (below: a parameter per edge, anchors): a per-edge l / d is an exact input and 1/d^2 costs the same 2 on the device;
+//           an anchor's t_c = fl(x_pc - a_c) is 1, its (psi, a, b, v) the neighbour's, and it adds one fma to each chain of its row: deg becomes
+//           D = the largest (neighbours + anchors) of a point in the three row-sum counts and in f's (tests/test_sphess_pair_ex.py).
 #include <math.h>
 
 #include "sphess.h"
@@ -101,8 +104,9 @@ struct PairRow {
         e = g = d = m0 = m1 = 0.0;
         kin = -1;
     }
-    // slot k holding (j, w): true and the new value in h when the slot is a cross-point entry
-    __device__ __forceinline__ bool slot(const PairPot<KIND>& pot, const double* x, double scale, int k, int32_t j, double w, double& h) {
+    // slot k holding (j, w): true and the new value in h when the slot is a cross-point entry; pot: PairPot<KIND>, or PairPotAt<KIND> (below)
+    template <class POT>
+    __device__ __forceinline__ bool slot(const POT& pot, const double* x, double scale, int k, int32_t j, double w, double& h) {
         if (!on) return false;
         const int32_t jb = (j / DIM) * DIM;
         if (jb == base) {                           // the row itself (an empty slot) or another component of its point
@@ -191,8 +195,8 @@ struct PairRowF {
 
 // One slot of the edge form at owner row `row`: partner j, weight w.  A cross-point entry is the row kernel's expression from the owner's side; an
 // intra-point entry is copied from the owner's row of H's row form (at most dim - 1 such slots in a row; the row kernel ran before).
-template <int DIM, int KIND>
-__device__ __forceinline__ bool pair_own_slot(const PairPot<KIND>& pot, const double* x, double scale, const int32_t* ridx, const double* hrow, int64_t npad,
+template <int DIM, int KIND, class POT>
+__device__ __forceinline__ bool pair_own_slot(const POT& pot, const double* x, double scale, const int32_t* ridx, const double* hrow, int64_t npad,
                                               int Kr, int64_t row, bool valid, int64_t nrows, int32_t j, double w, double& h) {
     if (!valid || row >= nrows) return false;
     const int32_t r = (int32_t)row, base = (r / DIM) * DIM, jb = (j / DIM) * DIM;
@@ -250,6 +254,166 @@ struct PairOwnF {
     }
 };
 
+// ---- lfpsqp_sphess_pair_eval_ex: a parameter per edge (one more value stream on the pattern: the handle P) and anchors (lfpsqp_anchors) --------
+// The functors above keep their code; these two have their shape and go through the same PairRow::slot / pair_own_slot, with the potential of the
+// slot's own parameter.  "Has P" and "has anchors" are wave-uniform RUN-TIME tests (a null pointer, a width of 0), not template flags: four times
+// the 18 row kernels would buy nothing the resource report shows (FINDINGS.md 25: no scratch, the VGPRs of PairRowF + at most 14).
+// ROUNDINGS.  A per-edge l_e / delta_e is an exact input, as delta is, and 1/delta_e^2 = 1.0 / (delta_e delta_e) is the host's expression: every
+// count of the head of this file stands.  An anchor's t_c = fl(x_pc - a_c) is one rounding, (psi, a, b) and v are the neighbour's expressions, and
+// it adds one fma to each of the row's chains: with ka the most anchors on a point, deg becomes deg + ka in the counts of grad, diag and the
+// intra-point entry, and npoints deg becomes npoints (deg + ka) in f's (the factor 2 u of an anchor's energy term is exact).
+
+// The potential with the parameter of ONE slot; uni: the parameter is the call's delta and rd2 its 1 / delta^2 from the host (wave-uniform)
+template <int KIND>
+struct PairPotAt {
+    double par;
+    double rd2;
+    bool uni;
+    __device__ __forceinline__ void eval(double q, double& psi, double& a, double& b) const {
+        const PairPot<KIND> pot{par, KIND == 2 ? (uni ? rd2 : 1.0 / (par * par)) : 0.0};
+        pot.eval(q, psi, a, b);
+    }
+};
+
+// One anchor slot of a row, after its neighbours: weight u (0.0: an empty slot, skipped before anything else is loaded), position pos[base ..
+// base + dim - 1], parameter par[row] or the call's delta.  The sums take the terms PairRow::slot gives them for a neighbour at pos, in the same
+// expressions; the energy is counted at component 0 with 2 u (exact), because eval_finish halves the sum.  No entry between points is written.
+template <int DIM, int KIND, bool WF, bool WV>
+__device__ __forceinline__ void pair_anchor(PairRow<DIM, KIND, WF, WV>& r, const PairPot<KIND>& uni, const double* pos, const double* par, double u) {
+    if (!r.on || u == 0.0) return;
+    double t0, t1, t2, psi, a, b;
+    const double q = diff<DIM>(pos, r.xp0, r.xp1, r.xp2, r.base, t0, t1, t2);
+    const PairPotAt<KIND> pot{KIND != 0 && par ? par[r.r] : uni.delta, uni.rd2, !par};
+    pot.eval(q, psi, a, b);
+    const double tc = pick<DIM>(r.c, t0, t1, t2);
+    if (WF && r.c == 0) r.e = fma(u + u, psi, r.e);
+    if (WV) {
+        r.g = fma(u, a * tc, r.g);
+        if (KIND == 0) r.d = fma(u, 1.0, r.d);
+        else {
+            // the point's other components in increasing order, as slot() meets them: m0, then m1
+            r.d = fma(u, fma(b, tc * tc, a), r.d);
+            r.m0 = fma(u, b * (tc * pick<DIM>(r.c == 0 ? 1 : 0, t0, t1, t2)), r.m0);
+            if (DIM == 3) r.m1 = fma(u, b * (tc * pick<DIM>(r.c == 2 ? 1 : 2, t0, t1, t2)), r.m1);
+        }
+    }
+}
+
+template <bool WF, bool WV, int DIM, int KIND>
+struct PairRowExF {
+    PairPot<KIND> pot;         // the call's delta: the edges' parameter without pval, the anchors' without apar
+    const int32_t* idx;
+    const double* w;
+    const double* pval;        // P's row form, or nullptr
+    int64_t npad;
+    int K;
+    int64_t nrows;             // dim * npoints
+    const double* x;
+    double scale;
+    const double* apos;        // the anchors: aw slots of npad entries each
+    const double* au;
+    const double* apar;        // or nullptr
+    int aw;
+    double* grad;
+    double* diag;
+    double* hval;
+    __device__ __forceinline__ bool skip() const { return false; }
+    __device__ __forceinline__ void apply(int64_t i, bool v0, bool v1, double* red) const {
+        if (!v0 || i >= nrows) return;
+        PairRow<DIM, KIND, WF, WV> r0, r1;
+        r0.init(i, v0, nrows, x);
+        r1.init(i + 1, v1, nrows, x);
+        const int32_t* ip = idx + i;
+        const double* wp = w + i;
+        const bool uni = KIND == 0 || !pval;
+#pragma unroll 1
+        for (int k = 0; k < K; ++k) {
+            const int64_t o = (int64_t)k * npad;
+            const int2 jj = *reinterpret_cast<const int2*>(ip + o);
+            const double2 ww = ld2(wp + o);
+            const double2 pp = uni ? make_double2(pot.delta, pot.delta) : ld2(pval + i + o);
+            double h0 = 0.0, h1 = 0.0;
+            const bool s0 = r0.slot(PairPotAt<KIND>{pp.x, pot.rd2, uni}, x, scale, k, jj.x, ww.x, h0);
+            const bool s1 = r1.slot(PairPotAt<KIND>{pp.y, pot.rd2, uni}, x, scale, k, jj.y, ww.y, h1);
+            if (WV && hval) store_rows(hval, i, o, s0, s1, h0, h1);
+        }
+#pragma unroll 1
+        for (int k = 0; k < aw; ++k) {
+            const int64_t o = (int64_t)k * npad;
+            const double2 uu = ld2(au + i + o);
+            const double* pk = apar ? apar + o : nullptr;
+            pair_anchor(r0, pot, apos + o, pk, uu.x);
+            pair_anchor(r1, pot, apos + o, pk, uu.y);
+        }
+        if (WF) red[0] += r0.e + r1.e;
+        if (WV) {
+            if (hval) { r0.intra(scale, hval, npad); r1.intra(scale, hval, npad); }
+            if (grad) add_rows(grad, i, r1.on, scale, r0.g, r1.g);
+            if (diag) add_rows(diag, i, r1.on, scale, r0.d, r1.d);
+        }
+    }
+};
+
+// The edge form with P's edge form beside it: the two forms of P hold the same bits, so both sides evaluate (psi, a, b) from identical inputs.
+template <int DIM, int KIND>
+struct PairOwnExF {
+    const int32_t* idx;        // the edge form
+    const double* w;
+    const double* pval;        // P's edge form
+    int64_t npad;
+    int K;
+    const int32_t* ridx;       // the row form: the pattern, and H's values
+    const double* hrow;
+    int Kr;
+    int64_t nrows;
+    const double* x;
+    double scale;
+    double* hval;
+    __device__ __forceinline__ bool skip() const { return false; }
+    __device__ __forceinline__ void apply(int64_t i, bool v0, bool v1, double*) const {
+        if (!v0 || i >= nrows) return;
+        const int32_t* ip = idx + i;
+        const double* wp = w + i;
+#pragma unroll 1
+        for (int k = 0; k < K; ++k) {
+            const int64_t o = (int64_t)k * npad;
+            const int2 jj = *reinterpret_cast<const int2*>(ip + o);
+            const double2 ww = ld2(wp + o);
+            const double2 pp = ld2(pval + i + o);
+            double h0 = 0.0, h1 = 0.0;
+            const bool s0 = pair_own_slot<DIM, KIND>(PairPotAt<KIND>{pp.x, 0.0, false}, x, scale, ridx, hrow, npad, Kr, i, v0, nrows, jj.x, ww.x, h0);
+            const bool s1 = pair_own_slot<DIM, KIND>(PairPotAt<KIND>{pp.y, 0.0, false}, x, scale, ridx, hrow, npad, Kr, i + 1, v1, nrows, jj.y, ww.y, h1);
+            store_rows(hval, i, o, s0, s1, h0, h1);
+        }
+    }
+};
+
+template <int DIM, int KIND>
+static int pair_eval_ex_kind(lfpsqp_ctx* ctx, const lfpsqp_sphess* W, double delta, double rd2, const lfpsqp_sphess* P, const lfpsqp_anchors* A, double scale,
+                             const double* x, bool wantf, double* grad, double* diag, lfpsqp_sphess* H) {
+    const PairPot<KIND> pot{delta, rd2};
+    const int64_t nrows = (int64_t)DIM * W->pts.npoints;
+    const double* hr = H ? H->rval : nullptr;
+    double* he = H ? H->eval : nullptr;
+    auto launch = [&](const auto& own) {
+        return eval_launch<PairRowExF, DIM, KIND>(ctx, W, wantf, grad, diag, H, own, pot, W->ridx, W->rval, P ? P->rval : nullptr, W->npad, W->Kr, nrows, x,
+                                                  scale, A ? A->pos : nullptr, A ? A->u : nullptr, A ? A->par : nullptr, A ? A->width : 0);
+    };
+    if constexpr (KIND != 0) {
+        if (P) return launch(PairOwnExF<DIM, KIND>{W->eidx, W->eval, P->eval, W->npad, W->Ke, W->ridx, hr, W->Kr, nrows, x, scale, he});
+    }
+    // (the anchors write no entry between points: without P the edge form is the uniform call's)
+    return launch(PairOwnF<DIM, KIND>{pot, W->eidx, W->eval, W->npad, W->Ke, W->ridx, hr, W->Kr, nrows, x, scale, he});
+}
+
+template <int DIM>
+static int pair_eval_ex_dim(lfpsqp_ctx* ctx, const lfpsqp_sphess* W, int kind, double delta, double rd2, const lfpsqp_sphess* P, const lfpsqp_anchors* A,
+                            double scale, const double* x, bool wantf, double* grad, double* diag, lfpsqp_sphess* H) {
+    if (kind == 0) return pair_eval_ex_kind<DIM, 0>(ctx, W, delta, rd2, P, A, scale, x, wantf, grad, diag, H);
+    if (kind == 1) return pair_eval_ex_kind<DIM, 1>(ctx, W, delta, rd2, P, A, scale, x, wantf, grad, diag, H);
+    return pair_eval_ex_kind<DIM, 2>(ctx, W, delta, rd2, P, A, scale, x, wantf, grad, diag, H);
+}
+
 template <int DIM, int KIND>
 static int pair_eval_kind(lfpsqp_ctx* ctx, const lfpsqp_sphess* W, double delta, double rd2, double scale, const double* x, bool wantf, double* grad,
                           double* diag, lfpsqp_sphess* H) {
@@ -286,5 +450,25 @@ extern "C" int lfpsqp_sphess_pair_eval(lfpsqp_ctx* ctx, const lfpsqp_sphess* W, 
     double *gp = grad ? grad->p : nullptr, *dp = diag ? diag->p : nullptr;
     if (W->pts.dim == 2) LF_TRY(pair_eval_dim<2>(ctx, W, kind, delta, rd2, scale, x->p, f != nullptr, gp, dp, H));
     else LF_TRY(pair_eval_dim<3>(ctx, W, kind, delta, rd2, scale, x->p, f != nullptr, gp, dp, H));
+    return eval_finish(ctx, scale, f);
+}
+
+extern "C" int lfpsqp_sphess_pair_eval_ex(lfpsqp_ctx* ctx, const lfpsqp_sphess* W, int kind, double delta, const lfpsqp_sphess* P, const lfpsqp_anchors* A,
+                                          double scale, const lfpsqp_vec* x, double* f, lfpsqp_vec* grad, lfpsqp_vec* diag, lfpsqp_sphess* H) {
+    if (!P && !A) return lfpsqp_sphess_pair_eval(ctx, W, kind, delta, scale, x, f, grad, diag, H);
+    LF_ARG(ctx, ctx && W && x && kind >= 0 && kind <= 2 && std::isfinite(scale));
+    LF_ARG(ctx, W->pts.dim == 2 || W->pts.dim == 3);
+    const int64_t nrows = (int64_t)W->pts.dim * W->pts.npoints;
+    LF_ARG(ctx, !P || (kind != 0 && P != H && P->ridx == W->ridx && P->eidx == W->eidx));     // a handle on W's pattern; kind 0 has no parameter
+    LF_ARG(ctx, !A || (A->n == W->n && A->npoints == W->pts.npoints && A->dim == W->pts.dim && A->npad == W->npad));
+    const bool uses_delta = !P || (A && !A->par);
+    LF_ARG(ctx, !uses_delta || kind != 1 || (std::isfinite(delta) && delta >= 0.0));
+    LF_ARG(ctx, !uses_delta || kind != 2 || (std::isfinite(delta) && delta > 0.0));
+    LF_TRY(eval_check(ctx, "lfpsqp_sphess_pair_eval_ex", W, nrows, x, f, grad, diag, H));
+    if (nrows == 0 || !(f || grad || diag || H)) return 0;
+    const double rd2 = kind == 2 && uses_delta ? 1.0 / (delta * delta) : 0.0;
+    double *gp = grad ? grad->p : nullptr, *dp = diag ? diag->p : nullptr;
+    if (W->pts.dim == 2) LF_TRY(pair_eval_ex_dim<2>(ctx, W, kind, delta, rd2, P, A, scale, x->p, f != nullptr, gp, dp, H));
+    else LF_TRY(pair_eval_ex_dim<3>(ctx, W, kind, delta, rd2, P, A, scale, x->p, f != nullptr, gp, dp, H));
     return eval_finish(ctx, scale, f);
 }

@@ -496,25 +496,34 @@ class PointPotentialLinear(_PotentialSeparableLinear):
     (:meth:`SparseHessian.from_points`, N rows, never modified) holds w, ``sparse_hessian`` = ``weights.like()`` the current entries, rewritten
     with the diagonal by ``diag_objective_`` / ``diag_`` in one device call (lfpsqp_sphess_pair_eval) before every truncated-Newton solve, which
     ``optimize`` then runs as a :class:`SparseOperator` on lfpsqp_projcg_sparse.  At most 15 neighbours per point in 2-D, 10 in 3-D.  Kind 1 is
-    not convex where an edge is shorter than its rest length, and singular where two joined points coincide.  One rank."""
+    not convex where an edge is shorter than its rest length, and singular where two joined points coincide.  One rank.
+    ``rest``: one value per edge, aligned with ``edges`` (every edge once) -- the rest length l_e of kind 1 (a truss bar's natural length, a
+    measured distance), the delta_e of kind 2 -- which overrides ``delta`` on the edges.  ``anchors = (point, pos, u)`` or ``(point, pos, u,
+    par)``: the fixed points of :class:`PointAnchors` (supports, beacons), the term kappa sum_k u_k psi(x_p - a_k; par_k) with ``delta`` where no
+    ``par`` is given; at most 8 on a point.  Both are evaluated in the same device call (lfpsqp_sphess_pair_eval_ex)."""
 
     def __init__(self, ctx: Context, npoints: int, dim: int, m: int, Jct: DeviceMatrix, b, kind: int, a, c=0.0, edges=None, kappa: float = 1.0,
-                 pair_kind: int = 2, delta: float = 1.0, **kw):
+                 pair_kind: int = 2, delta: float = 1.0, rest=None, anchors=None, **kw):
         n = int(dim) * int(npoints)
         assert kw.get("n_global", n) in (None, n), "graph objective: one rank (the couplings would cross the shard boundaries)"
         assert edges is not None and len(edges) == 3, "point objective: edges = (pi, pj, w)"
         assert int(dim) in (2, 3), "point objective: dim 2 or 3"
         assert int(pair_kind) in (0, 1, 2), "point objective: pair_kind 0 .. 2"
         super().__init__(ctx, n, m, Jct, b, kind, a, c, **kw)
-        from .projcg import SparseHessian
+        from .projcg import PointAnchors, SparseHessian
         self.npoints, self.dim = int(npoints), int(dim)
         self.kappa, self.pair_kind, self.delta = float(kappa), int(pair_kind), float(delta)
         # N rows: the slack row, when the ball is there, has no edges
-        self._init_potential(SparseHessian.from_points(ctx, self.N, self.npoints, self.dim,
-                                                       *_edge_list(edges, npoints, "point objective: edges between the points")))
+        ei, ej, w = _edge_list(edges, npoints, "point objective: edges between the points")
+        self._init_potential(SparseHessian.from_points(ctx, self.N, self.npoints, self.dim, ei, ej, w))
+        # one l (kind 1) or delta (kind 2) per edge, aligned with `edges`: overrides `delta` on the edges (every edge once: a parameter does not add up)
+        self.params = None if rest is None else self.weights.point_values(ei, ej, rest)
+        # anchors = (point, pos, u) or (point, pos, u, par): kappa sum_k u_k psi(x_p - a_k; par_k), without par with `delta`
+        assert anchors is None or len(anchors) in (3, 4), "point objective: anchors = (point, pos, u) or (point, pos, u, par)"
+        self.anchors = None if anchors is None else PointAnchors(self.weights, *anchors)
 
     def _term(self, x, grad=None, diag=None, out=None, want_f=False):
-        return self.weights.pair_eval(self.pair_kind, self.delta, self.kappa, x, grad, diag, out, want_f)
+        return self.weights.pair_eval(self.pair_kind, self.delta, self.kappa, x, grad, diag, out, want_f, params=self.params, anchors=self.anchors)
 
 
 class SeparableElementwiseBox(SeparableLinearBallBox):

@@ -275,14 +275,40 @@ class SparseHessian:
         :meth:`like`.  With nothing but the value asked for, the kernel writes no vector.  This handle is never modified."""
         return self._eval("edge_eval", kind, delta, scale, x, grad, diag, out, want_f)
 
-    def pair_eval(self, kind: int, delta: float, scale: float, x, grad=None, diag=None, out=None, want_f: bool = True):
+    def point_values(self, pi, pj, vals) -> "SparseHessian":
+        """A handle on this pattern holding one PARAMETER per point edge (lfpsqp_sphess_points_values): ``vals[e]`` -- a rest length, a measured
+        distance; finite and >= 0 -- on all dim^2 entries of the point edge ``(pi[e], pj[e])`` and 0.0 inside a point: the ``params`` of
+        :meth:`pair_eval`.  The list must name every point edge of this handle (made by :meth:`from_points`, or a handle on its pattern) exactly
+        once, in any order and either orientation: a parameter does not add up, so a duplicate, a foreign edge or a missing one is refused."""
+        ii, jj, vv = _triplets("SparseHessian.point_values", "pi and pj", pi, pj, vals)
+        return object.__new__(SparseHessian)._open(self.ctx, self.ctx.L.lfpsqp_sphess_points_values, self.h, ii.size, ii.ctypes.data, jj.ctypes.data,
+                                                   vv.ctypes.data)
+
+    def _pair_eval_ex(self, kind, delta, params, anchors, scale, x, grad, diag, out, want_f):
+        ctx = self.ctx
+        for name, o in (("output handle", out), ("parameter handle", params), ("anchors", anchors)):
+            if o is not None and o.ctx is not ctx:
+                raise ValueError(f"SparseHessian.pair_eval: the {name} belongs to another context")
+        f = C.c_double()
+        h = lambda o: o.h if o is not None else None
+        ctx.check(ctx.L.lfpsqp_sphess_pair_eval_ex(ctx.h, self.h, int(kind), float(delta), h(params), h(anchors), float(scale), x.h,
+                                                   C.byref(f) if want_f else None, h(grad), h(diag), h(out)))
+        return f.value if want_f else None
+
+    def pair_eval(self, kind: int, delta: float, scale: float, x, grad=None, diag=None, out=None, want_f: bool = True, params=None, anchors=None):
         """The pair term scale * sum_e w_e psi(x_p - x_q) between the points of a handle made by :meth:`from_points`, with this handle's values as
         the weights (lfpsqp_sphess_pair_eval; t = x_p - x_q in R^dim, ``kind`` 0: |t|^2/2, 1: (|t| - delta)^2/2, a spring of rest length
         ``delta``, 2: the radial pseudo-Huber function delta^2 (sqrt(1 + |t|^2/delta^2) - 1)).  The conventions are those of :meth:`edge_eval`:
         the value is returned (None with ``want_f=False``), the gradient is ADDED to ``grad`` and the Hessian's diagonal to ``diag`` (their first
         dim*npoints entries; ``x`` may be longer), and ``out``, a handle made by :meth:`like`, receives the off-diagonal entries: the dim x dim
         block -(scale w)(a I + b t t') per edge and the entries between a point's own components.  This handle is never modified.  Kind 1 with
-        two coincident points joined by an edge is a singularity of the potential: the outputs are then not finite."""
+        two coincident points joined by an edge is a singularity of the potential: the outputs are then not finite.
+        ``params`` (a handle made by :meth:`point_values`): one rest length (kind 1) or one delta (kind 2) per edge instead of ``delta``; kind 0 has
+        no parameter and refuses it.  ``anchors`` (a :class:`PointAnchors` made for this handle) adds scale * sum_k u_k psi(x_p - a_k; par_k): to
+        the value, the gradient, the diagonal and the entries between a point's own components; no entry between points changes.  With either
+        the call is lfpsqp_sphess_pair_eval_ex, and ``delta`` is checked only where it is used (no ``params``, or anchors without ``par``)."""
+        if params is not None or anchors is not None:
+            return self._pair_eval_ex(kind, delta, params, anchors, scale, x, grad, diag, out, want_f)
         return self._eval("pair_eval", kind, delta, scale, x, grad, diag, out, want_f)
 
     @classmethod
@@ -303,6 +329,48 @@ class SparseHessian:
     def close(self):
         if self.h is not None:
             self.ctx.L.lfpsqp_sphess_free(self.ctx.h, self.h)
+            self.h = None
+
+    free = close
+
+    def __del__(self):
+        try:
+            if getattr(self.ctx, "h", None) is not None:
+                self.close()
+        except Exception:
+            pass
+
+
+class PointAnchors:
+    """Fixed points that points of ``W`` (a :class:`SparseHessian` made by :meth:`SparseHessian.from_points`, or a handle on its pattern) are tied
+    to (lfpsqp_anchors): anchor k ties point ``point[k]`` to the position ``pos[k]`` (nanchors x dim) with the weight ``u[k]`` (a scalar or one
+    per anchor) and the parameter ``par[k]`` -- the distance to keep from the anchor under kind 1 (0: a pin), the delta of kind 2; ``None``: the
+    ``delta`` of the call.  The supports of a truss, the beacons of a localisation problem: soft terms u_k psi(x_p - a_k; par_k), evaluated by
+    :meth:`SparseHessian.pair_eval` with ``anchors=`` this object.  At most 8 anchors on one point; ``nanchors`` and ``width`` (the most anchors
+    on one point) describe what was built.  The object keeps ``W``'s (n, npoints, dim), not ``W``: it may outlive it, and serves any handle with
+    those numbers."""
+
+    def __init__(self, W: SparseHessian, point, pos, u, par=None):
+        import numpy as np
+        self.ctx = ctx = W.ctx
+        self.h = None
+        pt = np.ascontiguousarray(np.asarray(point, dtype=np.int64).ravel())
+        ph = np.ascontiguousarray(np.asarray(pos, dtype=np.float64).reshape(pt.size, -1))
+        if ph.shape[1] != W.dim:
+            raise ValueError(f"PointAnchors: pos has {ph.shape[1]} columns for points of {W.dim} unknowns")
+        uh = np.ascontiguousarray(np.broadcast_to(np.asarray(u, dtype=np.float64), pt.shape))
+        rh = None if par is None else np.ascontiguousarray(np.broadcast_to(np.asarray(par, dtype=np.float64), pt.shape))
+        h = C.c_void_p()
+        ctx.check(ctx.L.lfpsqp_anchors_create(ctx.h, W.h, pt.size, pt.ctypes.data, ph.ctypes.data, uh.ctypes.data, None if rh is None else rh.ctypes.data,
+                                              C.byref(h)))
+        self.h = h
+        out = [_capi.c_i64() for _ in range(2)]
+        ctx.check(ctx.L.lfpsqp_anchors_info(self.h, *(C.byref(o) for o in out)))
+        self.nanchors, self.width = (o.value for o in out)
+
+    def close(self):
+        if self.h is not None:
+            self.ctx.L.lfpsqp_anchors_free(self.ctx.h, self.h)
             self.h = None
 
     free = close
